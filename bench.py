@@ -13,6 +13,11 @@ all-reduced over RCCL by ``p2p_pytorch_amd.parallel.GradReducer``.
 hipBLASLt, bf16 autocast, channels_last) -- the measured baseline of BASELINE.md.
 Rank 0 prints one JSON line; ``value`` = total images/sec over all ranks, from the MAX
 per-rank time of exactly K timed steps bracketed by barrier + device synchronize.
+
+A plain run sets up, warms up, times the K steps and prints that line -- nothing else.
+``--dump-outputs DIR`` also writes the last timed step's outputs as ``DIR/<name>.npy``;
+``--full`` adds the secondary measurements (the per-network all-reduce busy / exposed ms
+of a data-parallel run, taken in one extra eager step after the timed ones).
 """
 from __future__ import annotations
 
@@ -74,7 +79,25 @@ def parse():
                         " train.py:400-402) even though with the reference's optimizer_c it updates"
                         " nothing -- 1 (default) times the reference's full step")
     p.add_argument("--json_out", default=None)
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned (its loss "
+                        "scalars; --mode infer: the output mean) as DIR/<name>.npy in float32 "
+                        "(<name>_rank<r>.npy for N > 1).  Weights, inputs and dropout seeds are "
+                        "seeded, so two builds run with the same arguments compare output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements a plain run leaves out: with the gradient "
+                        "reducers attached (N > 1 or --force_comm), one extra eager step after the timed "
+                        "ones with timed collectives, reported per network under 'comm'")
     return p.parse_args()
+
+
+def dump_outputs(dirname, outputs, world, rank):
+    """Write each array of the last timed step's return value as ``<name>.npy`` (float32)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in outputs.items():
+        np.save(os.path.join(dirname, name if world == 1 else f"{name}_rank{rank}") + ".npy",
+                v.detach().to("cpu", torch.float32).numpy())
 
 
 def main():
@@ -208,12 +231,15 @@ def main():
     dt = time.perf_counter() - t0
     dt_max = pdist.max_scalar(dt, dev)
     loss_vals = {k: float(v) for k, v in losses.items()}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, losses, world, rank)
     comm = None
     if reducer_g is not None:
+        comm = {"dtype": args.comm_dtype, "bucket_mb": args.bucket_mb}
+    if reducer_g is not None and args.full:
         # after (never inside) the timed region: ONE eager step with the reducers' collectives
         # on a timed side stream -> per-network all-reduce busy ms, the part left exposed
         # after backward's last kernel, and the overlap fraction (max over ranks)
-        comm = {"dtype": args.comm_dtype, "bucket_mb": args.bucket_mb}
         if rank == 0:
             print("[bench] timed steps done; one eager step with timed collectives", file=sys.stderr, flush=True)
         for r in (reducer_g, reducer_d):

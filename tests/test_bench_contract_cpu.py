@@ -44,13 +44,38 @@ def test_bench_single_process_json_line():
     assert d["config"]["parallelism"] == "dp1"
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's outputs (the step's loss scalars)
+    as float32 ``DIR/<name>.npy``; weights, inputs and dropout are seeded, so a second run
+    with the same arguments writes the same arrays (single-threaded CPU: bitwise).  ``--full``
+    is accepted and leaves the result line's keys in place."""
+    import numpy as np
+    dumps = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--full", "--dump-outputs", str(d)] + ARGS,
+                           cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line, = _json_lines(r.stdout)
+        assert KEYS <= set(line)
+        arrs = {p.name[:-4]: np.load(p) for p in sorted(d.glob("*.npy"))}
+        assert set(arrs) == set(line["losses"]) and arrs
+        for k, a in arrs.items():
+            assert a.dtype == np.float32
+            assert float(a) == line["losses"][k]
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
 def test_bench_two_ranks_one_json_line():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2"] + ARGS,
+                        "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
+                        "--full"] + ARGS,
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -60,3 +85,6 @@ def test_bench_two_ranks_one_json_line():
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2"
     assert d["config"]["global_batch"] == 2 * d["config"]["per_gpu_batch"]   # weak scaling: per-GPU work fixed
     assert d["scaling"] == "weak"
+    # --full: the extra eager step with timed collectives reports per-network all-reduce figures
+    for tag in ("G", "D"):
+        assert d["comm"][tag]["comm_ms"] > 0 and d["comm"][tag]["buckets"] >= 1
