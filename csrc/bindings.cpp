@@ -73,6 +73,11 @@ int p2p_quantize_unshuffle(const void* x, int N, int H, int W, int C, int bits, 
 int p2p_metrics_ws(int C, int H, int W);
 int p2p_image_metrics(const void* a, const void* b, int dtype, const long* strides, int N, int C, int H, int W,
                       int shift, double data_range, double* ws, hipStream_t st);
+long p2p_ssim_loss_ws(int N, int C, int H, int W, int window);
+int p2p_ssim_loss_fwd(const void* x, const void* y, int dtype, const long* strides, int N, int C, int H, int W,
+                      int window, double data_range, float* ws, float* out, hipStream_t st);
+int p2p_ssim_loss_bwd(const void* x, const void* y, int dtype, const long* strides, int N, int C, int H, int W,
+                      int window, double data_range, const float* gout, void* dx, hipStream_t st);
 int p2p_avgpool3s2(const void* x, int N, int H, int W, int C, int OH, int OW, void* y, int bwd, hipStream_t st);
 int p2p_maxpool2(const void* x, const void* gy, int N, int H, int W, int C, void* out, hipStream_t st);
 int p2p_l2norm(const void* x, const void* gy, long P, int C, float eps, const void* res, void* out, int r, int IH,
@@ -1437,6 +1442,57 @@ Tensor image_metrics(const Tensor& a, const Tensor& b, bool shift, double data_r
   return at::stack({psnr, ssim}, 1);
 }
 
+// SSIM loss (csrc/ssim_loss.hip): two [N, C, H, W] images of one shape and dtype (fp32 or
+// bf16), any strides.  window: 0 = uniform7, 1 = gauss11.
+static void check_ssim(const Tensor& x, const Tensor& y, int64_t window, const char* what) {
+  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.dim() == 4 && x.sizes() == y.sizes(), what,
+              ": two 4-D CUDA tensors of one shape");
+  TORCH_CHECK(x.scalar_type() == y.scalar_type() &&
+                  (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
+              what, ": fp32 or bf16 inputs of one dtype");
+  TORCH_CHECK(window == 0 || window == 1, what, ": window 0 (uniform7) or 1 (gauss11)");
+  const int64_t k = window == 1 ? 11 : 7;
+  TORCH_CHECK(x.size(2) >= k && x.size(3) >= k, what, ": images of at least ", k, "x", k, " (the window)");
+}
+
+Tensor ssim_loss_fwd(const Tensor& x, const Tensor& y, int64_t window, double data_range) {
+  check_ssim(x, y, window, "ssim_loss_fwd");
+  const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
+  const long st[8] = {(long)x.stride(0), (long)x.stride(1), (long)x.stride(2), (long)x.stride(3),
+                      (long)y.stride(0), (long)y.stride(1), (long)y.stride(2), (long)y.stride(3)};
+  Tensor ws = at::empty({p2p_ssim_loss_ws(N, C, H, W, (int)window)}, x.options().dtype(at::kFloat));
+  Tensor out = at::empty({}, x.options().dtype(at::kFloat));
+  check_rc(p2p_ssim_loss_fwd(x.data_ptr(), y.data_ptr(), x.scalar_type() == at::kBFloat16 ? 1 : 0, st, N, C, H,
+                             W, (int)window, data_range, ws.data_ptr<float>(), out.data_ptr<float>(),
+                             cur_stream(x)),
+           "ssim_loss_fwd");
+  return out;
+}
+
+// {dL/dx, dL/dy} (undefined where not needed), each laid out like its image
+std::vector<Tensor> ssim_loss_bwd(const Tensor& x, const Tensor& y, int64_t window, double data_range,
+                                  const Tensor& gout, bool need_x, bool need_y) {
+  check_ssim(x, y, window, "ssim_loss_bwd");
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "ssim_loss_bwd: gout");
+  Tensor g = gout.contiguous();
+  const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
+  const int dt = x.scalar_type() == at::kBFloat16 ? 1 : 0;
+  auto run = [&](const Tensor& a, const Tensor& b) {   // dL/da: S is symmetric in its two images
+    Tensor d = at::empty_like(a);
+    const long st[12] = {(long)a.stride(0), (long)a.stride(1), (long)a.stride(2), (long)a.stride(3),
+                         (long)b.stride(0), (long)b.stride(1), (long)b.stride(2), (long)b.stride(3),
+                         (long)d.stride(0), (long)d.stride(1), (long)d.stride(2), (long)d.stride(3)};
+    check_rc(p2p_ssim_loss_bwd(a.data_ptr(), b.data_ptr(), dt, st, N, C, H, W, (int)window, data_range,
+                               g.data_ptr<float>(), d.data_ptr(), cur_stream(a)),
+             "ssim_loss_bwd");
+    return d;
+  };
+  Tensor gx, gy;
+  if (need_x) gx = run(x, y);
+  if (need_y) gy = run(y, x);
+  return {gx, gy};
+}
+
 Tensor tv_bwd(const Tensor& x, const Tensor& gout) {
   check_nhwc(x, "tv_bwd");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
@@ -1997,6 +2053,9 @@ TORCH_LIBRARY(p2p, m) {
   m.def("prelu_bwd(Tensor x, Tensor gy, Tensor w, bool need_x) -> Tensor[]");
   m.def("tv_fwd(Tensor x) -> Tensor");
   m.def("tv_bwd(Tensor x, Tensor gout) -> Tensor");
+  m.def("ssim_loss_fwd(Tensor x, Tensor y, int window, float data_range) -> Tensor");
+  m.def("ssim_loss_bwd(Tensor x, Tensor y, int window, float data_range, Tensor gout, bool need_x, "
+        "bool need_y) -> Tensor[]");
   m.def("quantize(Tensor x, int bits) -> Tensor");
   m.def("quantize_unshuffle(Tensor x, int bits, int r, int cp) -> Tensor[]");
   m.def("image_metrics(Tensor a, Tensor b, bool shift, float data_range) -> Tensor");
@@ -2072,6 +2131,8 @@ TORCH_LIBRARY_IMPL(p2p, CUDA, m) {
   m.impl("prelu_bwd", prelu_bwd);
   m.impl("tv_fwd", tv_fwd);
   m.impl("tv_bwd", tv_bwd);
+  m.impl("ssim_loss_fwd", ssim_loss_fwd);
+  m.impl("ssim_loss_bwd", ssim_loss_bwd);
   m.impl("quantize", quantize);
   m.impl("quantize_unshuffle", quantize_unshuffle);
   m.impl("image_metrics", image_metrics);

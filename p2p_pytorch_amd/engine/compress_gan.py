@@ -64,7 +64,8 @@ class CompressGANStep:
     def __init__(self, net_g, net_d, net_c, lr=2e-4, beta1=0.5, bits=3, lambda_feat=10.0,
                  lambda_vgg=10.0, lambda_tv=1.0, n_layers_d=3, num_d=3, image_pool=None,
                  train_c=False, c_phase_backward=False, vgg=None, reducer_g=None,
-                 reducer_d=None, reducer_c=None, nan_guard=True):
+                 reducer_d=None, reducer_c=None, nan_guard=True, lambda_ssim=0.0,
+                 ssim_window="uniform7"):
         self.net_g, self.net_d, self.net_c = net_g, net_d, net_c
         self.criterionGAN = GANLoss()                      # LSGAN, reference default
         self.criterionVGG = vgg if vgg is not None else VGGLoss()
@@ -72,6 +73,8 @@ class CompressGANStep:
         self.criterionVGG.to(dev)
         self.bits = bits
         self.lambda_feat, self.lambda_vgg, self.lambda_tv = lambda_feat, lambda_vgg, lambda_tv
+        # optional structural term lambda_ssim * (1 - SSIM(fake_b, real_b)); 0 = not built
+        self.lambda_ssim, self.ssim_window = float(lambda_ssim), ssim_window
         self.feat_weights = 4.0 / (n_layers_d + 1)
         self.d_weights = 1.0 / num_d
         self.opt_g = make_adam(net_g.parameters(), lr=lr, betas=(beta1, 0.999))
@@ -186,7 +189,8 @@ class CompressGANStep:
         # ---- G losses: D frozen (its G-loss gradients are discarded by the reference)
         set_requires_grad(self._d_trainable, False)
         # fake_b feeds D, VGG and TV: one fan-out node sums their gradients with HIP adds
-        fake_d, fake_v, fake_t = ops.fan_out(fake_b, 3)
+        use_ssim = self.lambda_ssim > 0
+        fake_d, fake_v, fake_t, *fake_s = ops.fan_out(fake_b, 4 if use_ssim else 3)
         pred_fake_g = D(self._d_in(real_a, fake_d))
         # back on before any backward: autograd's AccumulateGrad skips a leaf that no longer
         # requires grad, which would silently drop the D-loss gradients
@@ -214,15 +218,20 @@ class CompressGANStep:
                    and os.environ.get("P2P_VGG_REUSE", "1") != "0" else None)
         vgg_g = self._vgg(fake_v, real_b, fy_real)
         tv = calc_tv_Loss(fake_t)
+        ssim = ops.ssim_loss(fake_s[0], real_b, self.ssim_window) if use_ssim else None
         if native:
             terms = [loss_g_gan] + ([loss_feat] if feat else []) + [vgg_g, tv]
-            loss_g = ops.lincomb_n(terms, [1.0] + ([1.0] if feat else []) + [self.lambda_vgg,
-                                                                           self.lambda_tv])
+            weights = [1.0] + ([1.0] if feat else []) + [self.lambda_vgg, self.lambda_tv]
+            if use_ssim:
+                terms, weights = terms + [ssim], weights + [self.lambda_ssim]
+            loss_g = ops.lincomb_n(terms, weights)
             with torch.no_grad():
                 content = ops.lincomb_n([vgg_g.detach()], [self.lambda_vgg])
         else:
             content = vgg_g * self.lambda_vgg
             loss_g = loss_g_gan + loss_feat + content + tv * self.lambda_tv
+            if use_ssim:
+                loss_g = loss_g + ssim * self.lambda_ssim
         # ---- updates: G first (its backward also reaches D; those grads are dropped)
         with self._phase("G_bwd_opt"):
             self._zero(self.opt_g, self.reducer_g)
@@ -264,6 +273,9 @@ class CompressGANStep:
             with paused_g:      # reference: grads land on G (zeroed next step) -- no effect
                 loss_c.backward(self._seed_grad(loss_c))
             self._no_deferred(real_a)
-        return {"D": loss_d.detach(), "G_GAN": loss_g_gan.detach(),
-                "C": loss_c.detach(), "G_GAN_Feat": torch.as_tensor(loss_feat).detach(),
-                "VGG": content.detach(), "TV": tv.detach(), "G": loss_g.detach()}
+        out = {"D": loss_d.detach(), "G_GAN": loss_g_gan.detach(),
+               "C": loss_c.detach(), "G_GAN_Feat": torch.as_tensor(loss_feat).detach(),
+               "VGG": content.detach(), "TV": tv.detach(), "G": loss_g.detach()}
+        if use_ssim:
+            out["SSIM"] = ssim.detach()
+        return out

@@ -7,8 +7,9 @@ backward -- SURVEY.md section 5.8):
   2. D phase: ``D(cat(A, fake_B.detach()))`` vs fake label, ``D(cat(A, B))`` vs real label,
      ``loss_D = 0.5 * (fake + real)`` -> backward -> all-reduce D grads -> Adam(D)
   3. G phase (D params frozen, so D only back-propagates to its input):
-     ``D(cat(A, fake_B))`` vs real label + ``lambda_L1 * |fake_B - B|`` -> backward ->
-     all-reduce G grads -> Adam(G)
+     ``D(cat(A, fake_B))`` vs real label + ``lambda_L1 * |fake_B - B|`` (+ ``lambda_ssim *
+     (1 - SSIM(fake_B, B))`` when that weight is set) -> backward -> all-reduce G grads ->
+     Adam(G)
 
 The concat of (A, fake_B) is a *virtual* concat on the native path: D's first conv reads
 the two images through two base pointers (``ops.conv2d`` accepts a tuple input).
@@ -24,7 +25,7 @@ from .. import _native
 from ..models.compress_gan import MultiscaleDiscriminator
 from ..models.layers import BatchNorm2d
 from ..models.losses import GANLoss
-from ..ops import l1
+from ..ops import l1, ssim_loss
 from ..utils.tracing import trace_range
 from .optim import guarded_step, make_adam
 
@@ -38,10 +39,12 @@ def set_requires_grad(nets, flag: bool):
 class Pix2PixStep:
     def __init__(self, netG, netD, lr=2e-4, beta1=0.5, gan_mode="vanilla", lambda_L1=100.0,
                  reducer_g=None, reducer_d=None, autocast_dtype=None, fuse_d_batch=None,
-                 nan_guard=True, packed=None):
+                 nan_guard=True, packed=None, lambda_ssim=0.0, ssim_window="uniform7"):
         self.netG, self.netD = netG, netD
         self.criterionGAN = GANLoss(gan_mode=gan_mode)
         self.lambda_L1 = float(lambda_L1)
+        # optional structural term lambda_ssim * (1 - SSIM(fake_B, real_B)); 0 = not built
+        self.lambda_ssim, self.ssim_window = float(lambda_ssim), ssim_window
         self.opt_G = make_adam(netG.parameters(), lr=lr, betas=(beta1, 0.999))
         self.opt_D = make_adam(netD.parameters(), lr=lr, betas=(beta1, 0.999))
         self.reducer_g, self.reducer_d = reducer_g, reducer_d
@@ -116,6 +119,10 @@ class Pix2PixStep:
         on 3 + 3 channel images, the 2B D batch, vanilla / lsgan losses."""
         from ..models.pix2pix import NLayerDiscriminator, PixelDiscriminator, UnetGenerator
         if self.packed is False or self.fuse_d_batch is False or not self.d_per_sample:
+            return False
+        if self.lambda_ssim > 0:
+            # the packed step keeps fake_B only inside the pair tensor, whose gradient is
+            # produced by D's first-conv dgrad: no tensor for a second image loss to read
             return False
         if not (isinstance(self.netG, UnetGenerator) and self.netG.packed_ok(real_A)):
             return False
@@ -234,6 +241,9 @@ class Pix2PixStep:
             loss_G_GAN = self.criterionGAN(pred_fake, True)
             loss_G_L1 = l1(fake_B, real_B) * self.lambda_L1
             loss_G = loss_G_GAN + loss_G_L1
+            if self.lambda_ssim > 0:
+                loss_G_SSIM = ssim_loss(fake_B, real_B, self.ssim_window)
+                loss_G = loss_G + loss_G_SSIM * self.lambda_ssim
         with self._phase("G_bwd_opt"):
             self._zero(self.opt_G, self.reducer_g)
             loss_G.backward()
@@ -243,5 +253,8 @@ class Pix2PixStep:
             if self.reducer_g is not None:
                 self.reducer_g.finish()
             self._guarded_step(self.opt_G, self.reducer_g, loss_G)
-        return {"D": loss_D.detach(), "G_GAN": loss_G_GAN.detach(), "G_L1": loss_G_L1.detach(),
-                "G": loss_G.detach()}
+        out = {"D": loss_D.detach(), "G_GAN": loss_G_GAN.detach(), "G_L1": loss_G_L1.detach(),
+               "G": loss_G.detach()}
+        if self.lambda_ssim > 0:
+            out["G_SSIM"] = loss_G_SSIM.detach()
+        return out

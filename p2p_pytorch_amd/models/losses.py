@@ -56,6 +56,18 @@ def calc_tv_Loss(x):
     return ops.tv(x)
 
 
+class SSIMLoss(nn.Module):
+    """1 - mean SSIM(pred, target) on model-range images (``ops.ssim_loss``): the continuous,
+    differentiable SSIM, not the uint8-level metric the trainer prints."""
+
+    def __init__(self, window="uniform7", data_range=2.0):
+        super().__init__()
+        self.window, self.data_range = window, float(data_range)
+
+    def forward(self, pred, target):
+        return ops.ssim_loss(pred, target, self.window, self.data_range)
+
+
 class angular_loss(nn.Module):
     """mean(acos(clamp(cos_sim_c(a, b)))) in degrees (networks.py:870-894)."""
 

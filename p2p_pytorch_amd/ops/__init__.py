@@ -153,6 +153,14 @@ def tv(x):
     return ref.tv(x)
 
 
+def ssim_loss(x, y, window="uniform7", data_range=2.0):
+    """1 - mean SSIM of two [N, C, H, W] images, differentiable in both (the continuous SSIM
+    of the values as given -- see ``reference.ssim_loss``)."""
+    if _native.use_native(x):
+        return _hip().ssim_loss(x, y, window, data_range)
+    return ref.ssim_loss(x, y, window, data_range)
+
+
 def quantize(x, bits, unshuffle=0):
     """``unshuffle`` r (HIP path): the same pass also writes the pixel-unshuffled, channel-
     padded copy that ``pixel_unshuffle(y, r, conv_input=True)`` hands to the next conv."""

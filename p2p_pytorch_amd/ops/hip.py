@@ -1830,6 +1830,38 @@ def tv(x):
     return TVFn.apply(x)
 
 
+SSIM_WINDOWS = {"uniform7": 0, "gauss11": 1}
+
+
+class SSIMLossFn(torch.autograd.Function):
+    """1 - mean SSIM (csrc/ssim_loss.hip).  Saves only the two images: the backward kernel
+    recomputes the window moments, so no per-origin map lives between the passes.  Inputs
+    are read through their strides (NHWC bf16, channel-padded views, NCHW fp32)."""
+
+    @staticmethod
+    def forward(ctx, x, y, window, data_range):
+        if y.dtype != x.dtype:
+            y = y.to(x.dtype)
+        ctx.window, ctx.data_range = window, data_range
+        ctx.save_for_backward(x, y)
+        return P().ssim_loss_fwd(x, y, window, data_range)
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, y = ctx.saved_tensors
+        nx, ny = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx, gy = P().ssim_loss_bwd(x, y, ctx.window, ctx.data_range, gout.float().reshape(1), nx, ny)
+        return (gx if nx else None), (gy if ny else None), None, None
+
+
+def ssim_loss(x, y, window="uniform7", data_range=2.0):
+    if window not in SSIM_WINDOWS:
+        raise ValueError(f"ssim_loss: unknown window {window!r} (uniform7 | gauss11)")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"ssim_loss: fp32 or bf16 images, got {x.dtype}")   # no silent upcast
+    return SSIMLossFn.apply(x, y, SSIM_WINDOWS[window], float(data_range))
+
+
 # y -> its unshuffled, channel-padded copy written by the same quantise pass (the expander's
 # head input); entries hold y, so a key never aliases a recycled allocation
 _unshuffled: dict = {}

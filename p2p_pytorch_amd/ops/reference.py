@@ -120,6 +120,46 @@ def tv(x: torch.Tensor) -> torch.Tensor:
             + torch.mean(torch.abs(x[:, :, :-1, :] - x[:, :, 1:, :])))
 
 
+def ssim_window(window: str, dtype=torch.float64, device=None):
+    """(1-D taps summing to 1, covariance factor) of a separable SSIM window."""
+    if window == "uniform7":
+        return torch.full((7,), 1.0 / 7.0, dtype=dtype, device=device), 49.0 / 48.0
+    if window == "gauss11":
+        d = torch.arange(11, dtype=torch.float64) - 5.0
+        g = torch.exp(-d * d / (2.0 * 1.5 * 1.5))
+        return (g / g.sum()).to(dtype=dtype, device=device), 1.0
+    raise ValueError(f"ssim_loss: unknown window {window!r} (uniform7 | gauss11)")
+
+
+def ssim_loss(x: torch.Tensor, y: torch.Tensor, window: str = "uniform7",
+              data_range: float = 2.0) -> torch.Tensor:
+    """1 - mean SSIM over n, c and the valid window origins.
+
+    The CONTINUOUS SSIM of the values as given (model range [-1, 1], ``data_range`` 2): no
+    clamp and no uint8 quantisation, which have zero gradient -- deliberately not the
+    integer-level metric of ``engine.metrics.image_metrics``.  ``uniform7``: 7x7 box with the
+    sample covariance factor 49/48 (that metric's window); ``gauss11``: 11x11 Gaussian,
+    sigma 1.5, factor 1 (Wang et al.).  Keeps the dtype it is given (half types go to fp32).
+    """
+    if x.dtype in (torch.bfloat16, torch.float16):
+        x = x.float()
+    y = y.to(x.dtype)
+    g, f = ssim_window(window, x.dtype, x.device)
+    C, k = x.shape[1], g.numel()
+    w = (g[:, None] * g[None, :]).expand(C, 1, k, k).contiguous()
+
+    def E(t):
+        return F.conv2d(t, w, groups=C)
+
+    ux, uy = E(x), E(y)
+    vx = f * (E(x * x) - ux * ux)
+    vy = f * (E(y * y) - uy * uy)
+    vxy = f * (E(x * y) - ux * uy)
+    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    s = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
+    return 1.0 - s.mean()
+
+
 def quantize(x: torch.Tensor, bits: int) -> torch.Tensor:
     """round(clamp(x,0,1)*(2^b-1))/(2^b-1) (reference ``compress``, generate_dataset.py:29-34)."""
     m = float(2 ** bits - 1)

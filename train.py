@@ -63,6 +63,10 @@ def build_parser():
     p.add_argument("--threads", type=int, default=4, help="number of threads for data loader")
     p.add_argument("--seed", type=int, default=123, help="random seed to use. Default=123")
     p.add_argument("--lamb", type=float, default=10, help="weight on L1 term in objective")
+    p.add_argument("--lambda_ssim", type=float, default=0.0,
+                   help="weight on the SSIM loss term 1 - SSIM(fake, real) of the G objective (0 = off)")
+    p.add_argument("--ssim_window", default="uniform7", choices=["uniform7", "gauss11"],
+                   help="SSIM loss window: 7x7 box (the printed metric's) or 11x11 Gaussian")
     # ---- new
     p.add_argument("--netG", default="expand", help="expand | unet_256 | unet_128 | unet_<levels>")
     p.add_argument("--netD", default=None, help="multiscale | basic | n_layers | pixel")
@@ -198,7 +202,8 @@ def main(argv=None):
                               gan_mode=opt.gan_mode or "vanilla", lambda_L1=opt.lamb,
                               reducer_g=reducer_g, reducer_d=reducer_d,
                               autocast_dtype=torch.bfloat16 if (use_cuda and p2p.get_backend() == "torch") else None,
-                              nan_guard=not opt.no_nan_guard)
+                              nan_guard=not opt.no_nan_guard,
+                              lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window)
         opt_g, opt_d = trainer.opt_G, trainer.opt_D
     else:
         from p2p_pytorch_amd.engine.compress_gan import CompressGANStep
@@ -207,7 +212,8 @@ def main(argv=None):
                                   n_layers_d=opt.n_layers_D, image_pool=ImagePool(0),
                                   train_c=opt.train_c, c_phase_backward=opt.c_phase_backward,
                                   reducer_g=reducer_g, reducer_d=reducer_d, reducer_c=reducer_c,
-                                  nan_guard=not opt.no_nan_guard)
+                                  nan_guard=not opt.no_nan_guard,
+                                  lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window)
         opt_g, opt_d = trainer.opt_g, trainer.opt_d
     # the reference's third optimizer / scheduler pair (train.py:243-246, :441-443): over C
     # when --train_c fixes quirk A1, and stepped + checkpointed like the other two
