@@ -78,6 +78,8 @@ int p2p_ssim_loss_fwd(const void* x, const void* y, int dtype, const long* strid
                       int window, double data_range, float* ws, float* out, hipStream_t st);
 int p2p_ssim_loss_bwd(const void* x, const void* y, int dtype, const long* strides, int N, int C, int H, int W,
                       int window, double data_range, const float* gout, void* dx, hipStream_t st);
+int p2p_augment_pairs(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
+                      int CH, int CW, int dtype, void* out_a, void* out_b, hipStream_t st);
 int p2p_avgpool3s2(const void* x, int N, int H, int W, int C, int OH, int OW, void* y, int bwd, hipStream_t st);
 int p2p_maxpool2(const void* x, const void* gy, int N, int H, int W, int C, void* out, hipStream_t st);
 int p2p_l2norm(const void* x, const void* gy, long P, int C, float eps, const void* res, void* out, int r, int IH,
@@ -1493,6 +1495,50 @@ std::vector<Tensor> ssim_loss_bwd(const Tensor& x, const Tensor& y, int64_t wind
   return {gx, gy};
 }
 
+// Random resize / crop / flip of cached pairs (csrc/augment.hip).  a, b: the uint8 [N, H, W, 3]
+// cache; params: int32 [B, 4] rows (index, y0, x0, flip).  A CPU table is range-checked here
+// and copied up; a device table is trusted (the kernel clamps each row into range, so a bad
+// row never reads outside the cache).  dtype: 0 = fp32, 1 = bf16.  Returns {a', b'}, each
+// [B, 3, CH, CW] channels_last in [-1, 1].
+std::vector<Tensor> augment_pairs(const Tensor& a, const Tensor& b, const Tensor& params, int64_t LH, int64_t LW,
+                                  int64_t CH, int64_t CW, int64_t dtype) {
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.device() == b.device(), "augment_pairs: a, b on one GPU");
+  TORCH_CHECK(a.scalar_type() == at::kByte && b.scalar_type() == at::kByte && a.dim() == 4 && a.size(3) == 3 &&
+                  a.sizes() == b.sizes() && a.is_contiguous() && b.is_contiguous(),
+              "augment_pairs: two contiguous uint8 [N, H, W, 3] tensors of one shape");
+  const int64_t N = a.size(0), H = a.size(1), W = a.size(2);
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "augment_pairs: empty cache");
+  TORCH_CHECK(LH >= H && LW >= W, "augment_pairs: load size ", LH, "x", LW, " is smaller than the images (", H, "x",
+              W, "): only magnification or identity");
+  TORCH_CHECK(CH >= 1 && CH <= LH && CW >= 1 && CW <= LW, "augment_pairs: crop ", CH, "x", CW,
+              " does not fit the load size ", LH, "x", LW);
+  TORCH_CHECK(2 * LH * (H + 1) <= INT32_MAX && 2 * LW * (W + 1) <= INT32_MAX, "augment_pairs: sizes too large");
+  TORCH_CHECK(dtype == 0 || dtype == 1, "augment_pairs: dtype 0 (fp32) or 1 (bf16)");
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 4 && params.is_contiguous(),
+              "augment_pairs: params is a contiguous int32 [B, 4] tensor");
+  const int64_t B = params.size(0);
+  TORCH_CHECK(B <= 65535, "augment_pairs: at most 65535 samples per call");
+  Tensor p = params;
+  if (!params.is_cuda()) {
+    const int* r = params.data_ptr<int>();
+    for (int64_t i = 0; i < B; ++i, r += 4)
+      TORCH_CHECK(r[0] >= 0 && r[0] < N && r[1] >= 0 && r[1] <= LH - CH && r[2] >= 0 && r[2] <= LW - CW &&
+                      (r[3] == 0 || r[3] == 1),
+                  "augment_pairs: params row ", i, " = (", r[0], ", ", r[1], ", ", r[2], ", ", r[3],
+                  ") is out of range");
+    p = params.to(a.device());
+  } else {
+    TORCH_CHECK(params.device() == a.device(), "augment_pairs: params on another GPU than the cache");
+  }
+  const auto opt = a.options().dtype(dtype == 1 ? at::kBFloat16 : at::kFloat).memory_format(at::MemoryFormat::ChannelsLast);
+  Tensor oa = at::empty({B, 3, CH, CW}, opt), ob = at::empty({B, 3, CH, CW}, opt);
+  if (B == 0) return {oa, ob};
+  check_rc(p2p_augment_pairs(a.data_ptr(), b.data_ptr(), p.data_ptr<int>(), (int)N, (int)H, (int)W, (int)B, (int)LH,
+                             (int)LW, (int)CH, (int)CW, (int)dtype, oa.data_ptr(), ob.data_ptr(), cur_stream(a)),
+           "augment_pairs");
+  return {oa, ob};
+}
+
 Tensor tv_bwd(const Tensor& x, const Tensor& gout) {
   check_nhwc(x, "tv_bwd");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
@@ -2056,6 +2102,7 @@ TORCH_LIBRARY(p2p, m) {
   m.def("ssim_loss_fwd(Tensor x, Tensor y, int window, float data_range) -> Tensor");
   m.def("ssim_loss_bwd(Tensor x, Tensor y, int window, float data_range, Tensor gout, bool need_x, "
         "bool need_y) -> Tensor[]");
+  m.def("augment_pairs(Tensor a, Tensor b, Tensor params, int LH, int LW, int CH, int CW, int dtype) -> Tensor[]");
   m.def("quantize(Tensor x, int bits) -> Tensor");
   m.def("quantize_unshuffle(Tensor x, int bits, int r, int cp) -> Tensor[]");
   m.def("image_metrics(Tensor a, Tensor b, bool shift, float data_range) -> Tensor");
@@ -2133,6 +2180,7 @@ TORCH_LIBRARY_IMPL(p2p, CUDA, m) {
   m.impl("tv_bwd", tv_bwd);
   m.impl("ssim_loss_fwd", ssim_loss_fwd);
   m.impl("ssim_loss_bwd", ssim_loss_bwd);
+  m.impl("augment_pairs", augment_pairs);
   m.impl("quantize", quantize);
   m.impl("quantize_unshuffle", quantize_unshuffle);
   m.impl("image_metrics", image_metrics);

@@ -9,7 +9,10 @@ uint8 NHWC tensors that live in HBM (288 GB per GPU holds ~1.4 M 256x256 pairs),
 training batch is a device-side gather + uint8->bf16 normalise -- no DataLoader worker
 processes, no per-step host->device copies (the reference's only concurrency was
 DataLoader workers, train.py:174-175).  Each rank of a data-parallel job draws its own
-disjoint slice of a shared per-epoch permutation.
+disjoint slice of a shared per-epoch permutation.  With ``load_size`` / ``crop_size`` /
+``flip`` it also applies pix2pix's augmentation (resize to the load size, one random crop,
+one random horizontal flip, the same for both images of a pair) in the same single pass
+over the cache (``ops.augment_pairs``).
 """
 from __future__ import annotations
 
@@ -21,6 +24,7 @@ import torch
 import torch.utils.data as data
 from PIL import Image
 
+from .. import ops
 from .image_io import is_image_file, normalize, to_tensor
 
 
@@ -52,10 +56,15 @@ def get_test_set(root_dir, direction="b2a"):
 
 class DevicePairCache:
     """All pairs of a folder split as uint8 [N, H, W, 3] on ``device``; images must share
-    one size (the generator's crops do)."""
+    one size (the generator's crops do).
+
+    ``load_size`` (int or (h, w), at least the image size), ``crop_size`` (int or (h, w),
+    default the load size) and ``flip`` switch the augmentation on: every epoch draws one
+    (y0, x0, flip) per sample next to the permutation, uniform over 0 .. load - crop and
+    {0, 1}.  With all three at their defaults a batch is the plain gather + normalise."""
 
     def __init__(self, dataset: DatasetFromFolder, device, rank: int = 0, world: int = 1,
-                 seed: int = 123):
+                 seed: int = 123, load_size=None, crop_size=None, flip: bool = False):
         a_list, b_list = [], []
         for name in dataset.image_filenames:
             a_list.append(np.asarray(Image.open(join(dataset.a_path, name)).convert("RGB")))
@@ -77,6 +86,20 @@ class DevicePairCache:
         self.gen = torch.Generator(device="cpu").manual_seed(seed)
         self._perm = None
         self._pos = 0
+        self.augment = load_size is not None or crop_size is not None or bool(flip)
+        self.flip = bool(flip)
+        size = tuple(self.a.shape[1:3])
+        self.load = size if load_size is None else self._hw(load_size)
+        self.crop = self.load if crop_size is None else self._hw(crop_size)
+        if self.load[0] < size[0] or self.load[1] < size[1]:
+            raise ValueError(f"load_size {self.load} is smaller than the images {size}")
+        if not (1 <= self.crop[0] <= self.load[0] and 1 <= self.crop[1] <= self.load[1]):
+            raise ValueError(f"crop_size {self.crop} does not fit load_size {self.load}")
+        self._table = None   # int32 [n, 4] on the device: (index, y0, x0, flip) of this epoch
+
+    @staticmethod
+    def _hw(v):
+        return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
 
     def __len__(self):
         return self.n
@@ -91,8 +114,18 @@ class DevicePairCache:
             memory_format=torch.channels_last)
 
     def new_epoch(self):
-        self._perm = torch.randperm(self.n, generator=self.gen).to(self.device)
+        perm = torch.randperm(self.n, generator=self.gen)
+        self._perm = perm.to(self.device)
         self._pos = 0
+        if self.augment:
+            # every rank draws the same table from the same generator and takes its slice
+            def draw(high):
+                return torch.randint(0, high, (self.n,), generator=self.gen)
+
+            y0 = draw(self.load[0] - self.crop[0] + 1)
+            x0 = draw(self.load[1] - self.crop[1] + 1)
+            fl = draw(2) if self.flip else torch.zeros(self.n, dtype=torch.long)
+            self._table = torch.stack([perm, y0, x0, fl], 1).to(torch.int32).to(self.device)
 
     def next_batch(self, batch_size: int, dtype=torch.bfloat16):
         """Next (input, target) batch of this rank; None at the end of the epoch."""
@@ -101,7 +134,10 @@ class DevicePairCache:
         span = batch_size * self.world
         if self._pos + span > self.n:
             return None
-        idx = self._perm[self._pos + self.rank * batch_size:self._pos + (self.rank + 1) * batch_size]
+        lo = self._pos + self.rank * batch_size
         self._pos += span
+        if self.augment:   # one pass over the cache, one rounding
+            return ops.augment_pairs(self.a, self.b, self._table[lo:lo + batch_size], self.load, self.crop, dtype)
+        idx = self._perm[lo:lo + batch_size]
         return self._to_model(self.a.index_select(0, idx), dtype), self._to_model(
             self.b.index_select(0, idx), dtype)

@@ -160,6 +160,45 @@ def ssim_loss(x: torch.Tensor, y: torch.Tensor, window: str = "uniform7",
     return 1.0 - s.mean()
 
 
+def augment_pairs(a_u8: torch.Tensor, b_u8: torch.Tensor, params: torch.Tensor, load, crop,
+                  dtype=torch.bfloat16):
+    """Random resize / crop / flip of cached pairs (the oracle of csrc/augment.hip).
+
+    ``a_u8`` / ``b_u8``: uint8 [N, H, W, 3]; ``params``: int [B, 4] rows (index, y0, x0, flip);
+    ``load`` = (LH, LW) >= (H, W); ``crop`` = (CH, CW) <= load.  Each image is resized to
+    ``load`` by ``F.interpolate(mode="bicubic", align_corners=False)`` (skipped when it is the
+    source size), cropped at (y0, x0), flipped horizontally when ``flip``, clamped to
+    [0, 255] and scaled to [-1, 1].  Math in float32, or float64 when ``dtype`` is float64;
+    returns two [B, 3, CH, CW] channels_last tensors of ``dtype``.
+    """
+    (LH, LW), (CH, CW) = load, crop
+    N, H, W = a_u8.shape[:3]
+    if LH < H or LW < W:
+        raise ValueError(f"augment_pairs: load size {LH}x{LW} is smaller than the images ({H}x{W})")
+    if not (1 <= CH <= LH and 1 <= CW <= LW):
+        raise ValueError(f"augment_pairs: crop {CH}x{CW} does not fit the load size {LH}x{LW}")
+    rows = params.tolist()
+    for i, (idx, y0, x0, fl) in enumerate(rows):
+        if not (0 <= idx < N and 0 <= y0 <= LH - CH and 0 <= x0 <= LW - CW and fl in (0, 1)):
+            raise ValueError(f"augment_pairs: params row {i} = {(idx, y0, x0, fl)} is out of range")
+    compute = torch.float64 if dtype == torch.float64 else torch.float32
+    index = torch.tensor([r[0] for r in rows], dtype=torch.long, device=a_u8.device)
+
+    def one(src):
+        x = src.index_select(0, index).permute(0, 3, 1, 2).to(compute)
+        if (LH, LW) != (H, W):
+            x = F.interpolate(x, size=(LH, LW), mode="bicubic", align_corners=False)
+        out = []
+        for n, (_, y0, x0, fl) in enumerate(rows):
+            v = x[n, :, y0:y0 + CH, x0:x0 + CW]
+            out.append(torch.flip(v, dims=(2,)) if fl else v)
+        y = torch.stack(out) if out else x[:, :, :CH, :CW]
+        y = y.clamp(0.0, 255.0) * (2.0 / 255.0) - 1.0
+        return y.to(dtype).contiguous(memory_format=torch.channels_last)
+
+    return one(a_u8), one(b_u8)
+
+
 def quantize(x: torch.Tensor, bits: int) -> torch.Tensor:
     """round(clamp(x,0,1)*(2^b-1))/(2^b-1) (reference ``compress``, generate_dataset.py:29-34)."""
     m = float(2 ** bits - 1)

@@ -12,7 +12,8 @@ Two model families behind one CLI:
 MI355X additions: one process per GPU (launch with ``torchrun --nproc-per-node N``), RCCL
 gradient all-reduce bucketed and overlapped with backward (parallel/ddp.py), the HIP
 kernels (``--backend native``, default on GPU), optional whole-step hipGraph capture on
-one GPU (``--graph``), the dataset decoded once into HBM (``--device_cache``) or
+one GPU (``--graph``), the dataset decoded once into HBM (``--device_cache``, with pix2pix's
+resize / random crop / random flip as one HIP kernel: ``--load_size 286 --crop_size 256 --flip``) or
 synthetic pairs (``--synthetic``), JSONL metrics (``--log_json``), and checkpoints that
 really resume (``--epoch_count N`` or ``--resume``).
 """
@@ -81,6 +82,14 @@ def build_parser():
     p.add_argument("--steps_per_epoch", type=int, default=100, help="synthetic steps per epoch")
     p.add_argument("--device_cache", action="store_true",
                    help="decode the training set once into GPU memory (uint8) and batch there")
+    p.add_argument("--load_size", type=int, default=0,
+                   help="(--device_cache) resize each pair to this square size before the crop, "
+                        "e.g. 286 (0 = off: the image size)")
+    p.add_argument("--crop_size", type=int, default=0,
+                   help="(--device_cache) one random square crop of this size per pair, e.g. 256 "
+                        "(0 = the load size, or the image size)")
+    p.add_argument("--flip", action="store_true",
+                   help="(--device_cache) one random horizontal flip per pair")
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp8"],
                    help="(native) conv GEMM operand precision: bf16, or fp8 (e4m3 fwd / e5m2 dgrad)")
     p.add_argument("--deterministic", action="store_true",
@@ -130,6 +139,10 @@ def main(argv=None):
     if opt.cuda and not torch.cuda.is_available():
         raise Exception("No GPU found, please run without --cuda")
     device = pdist.local_device(local_rank) if use_cuda else torch.device("cpu")
+    augment = bool(opt.load_size or opt.crop_size or opt.flip)
+    if augment and not (opt.device_cache and use_cuda and not opt.synthetic):
+        raise SystemExit("--load_size / --crop_size / --flip augment the batches of the device cache: "
+                         "they need --device_cache on a GPU (--cuda) and a --dataset")
     if use_cuda:
         torch.cuda.set_device(device)
     p2p.set_backend(opt.backend or "native")
@@ -157,7 +170,9 @@ def main(argv=None):
         train_set = get_training_set(root, opt.direction)
         test_set = get_test_set(root, opt.direction)
         if opt.device_cache and use_cuda:
-            train_src = DevicePairCache(train_set, device, rank, world, seed=opt.seed)
+            train_src = DevicePairCache(train_set, device, rank, world, seed=opt.seed,
+                                        load_size=opt.load_size or None, crop_size=opt.crop_size or None,
+                                        flip=opt.flip)
         else:
             sampler = (torch.utils.data.distributed.DistributedSampler(
                 train_set, num_replicas=world, rank=rank, shuffle=True, seed=opt.seed)
