@@ -2014,6 +2014,9 @@ void adam(at::TensorList p, at::TensorList g, at::TensorList m, at::TensorList v
   TORCH_CHECK(!skip || skip->scalar_type() == at::kFloat, "adam: skip flag fp32");
   TORCH_CHECK(g.size() == n && m.size() == n && v.size() == n, "adam: list sizes");
   TORCH_CHECK(lr.scalar_type() == at::kFloat && step.scalar_type() == at::kFloat, "adam: lr/step fp32");
+  TORCH_CHECK(lr.is_cuda() && lr.numel() >= 1 && step.is_cuda() && step.numel() >= 1 &&
+                  (!skip || (skip->is_cuda() && skip->numel() >= 1)),
+              "adam: lr, step and skip are GPU tensors");
   const int maxT = p2p_adam_max_tensors();
   std::vector<float*> P, M, V;
   std::vector<const float*> G;
@@ -2032,7 +2035,10 @@ void adam(at::TensorList p, at::TensorList g, at::TensorList m, at::TensorList v
     TORCH_CHECK(p[i].scalar_type() == at::kFloat && p[i].is_contiguous() && g[i].is_contiguous() &&
                     m[i].is_contiguous() && v[i].is_contiguous() && g[i].scalar_type() == at::kFloat,
                 "adam: fp32 contiguous tensors");
+    TORCH_CHECK(m[i].scalar_type() == at::kFloat && v[i].scalar_type() == at::kFloat, "adam: fp32 moments");
+    TORCH_CHECK(p[i].is_cuda() && g[i].is_cuda() && m[i].is_cuda() && v[i].is_cuda(), "adam: GPU tensors");
     TORCH_CHECK(p[i].numel() == g[i].numel() && p[i].numel() < (1ll << 31), "adam: sizes");
+    TORCH_CHECK(m[i].numel() == p[i].numel() && v[i].numel() == p[i].numel(), "adam: moment sizes");
     P.push_back(p[i].data_ptr<float>());
     G.push_back(g[i].data_ptr<float>());
     M.push_back(m[i].data_ptr<float>());

@@ -16,7 +16,7 @@ def nonfinite(*tensors, counter=None) -> torch.Tensor:
     HIP kernel (csrc/elementwise.hip guard_flag); otherwise torch ops."""
     ts = [t for t in tensors if t is not None]
     if ts and all(t.is_cuda and t.dtype == torch.float32 and t.numel() == 1 for t in ts) \
-            and len(ts) <= 8 and (counter is None or counter.dtype == torch.float32):
+            and (counter is None or counter.dtype == torch.float32):   # > 8 scalars: the op raises
         from .. import _native
         if _native.get_backend() == "native" and _native.load():
             return _native.ops().guard_flag([t.detach() for t in ts], counter)
