@@ -80,6 +80,8 @@ int p2p_ssim_loss_bwd(const void* x, const void* y, int dtype, const long* strid
                       int window, double data_range, const float* gout, void* dx, hipStream_t st);
 int p2p_augment_pairs(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
                       int CH, int CW, int dtype, void* out_a, void* out_b, hipStream_t st);
+int p2p_augment_pairs_aa(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
+                         int CH, int CW, int dtype, void* out_a, void* out_b, hipStream_t st);
 int p2p_avgpool3s2(const void* x, int N, int H, int W, int C, int OH, int OW, void* y, int bwd, hipStream_t st);
 int p2p_maxpool2(const void* x, const void* gy, int N, int H, int W, int C, void* out, hipStream_t st);
 int p2p_l2norm(const void* x, const void* gy, long P, int C, float eps, const void* res, void* out, int r, int IH,
@@ -1499,20 +1501,29 @@ std::vector<Tensor> ssim_loss_bwd(const Tensor& x, const Tensor& y, int64_t wind
 // cache; params: int32 [B, 4] rows (index, y0, x0, flip).  A CPU table is range-checked here
 // and copied up; a device table is trusted (the kernel clamps each row into range, so a bad
 // row never reads outside the cache).  dtype: 0 = fp32, 1 = bf16.  Returns {a', b'}, each
-// [B, 3, CH, CW] channels_last in [-1, 1].
+// [B, 3, CH, CW] channels_last in [-1, 1].  antialias: the resize is PIL's bicubic
+// (F.interpolate(antialias=True)), and the load size may be smaller than the images, down to a
+// quarter of them.
 std::vector<Tensor> augment_pairs(const Tensor& a, const Tensor& b, const Tensor& params, int64_t LH, int64_t LW,
-                                  int64_t CH, int64_t CW, int64_t dtype) {
+                                  int64_t CH, int64_t CW, int64_t dtype, bool antialias) {
   TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.device() == b.device(), "augment_pairs: a, b on one GPU");
   TORCH_CHECK(a.scalar_type() == at::kByte && b.scalar_type() == at::kByte && a.dim() == 4 && a.size(3) == 3 &&
                   a.sizes() == b.sizes() && a.is_contiguous() && b.is_contiguous(),
               "augment_pairs: two contiguous uint8 [N, H, W, 3] tensors of one shape");
   const int64_t N = a.size(0), H = a.size(1), W = a.size(2);
   TORCH_CHECK(N >= 1 && H >= 1 && W >= 1, "augment_pairs: empty cache");
-  TORCH_CHECK(LH >= H && LW >= W, "augment_pairs: load size ", LH, "x", LW, " is smaller than the images (", H, "x",
-              W, "): only magnification or identity");
+  if (antialias) {
+    TORCH_CHECK(LH >= 1 && LW >= 1 && H <= 4 * LH && W <= 4 * LW, "augment_pairs: load size ", LH, "x", LW,
+                " is less than a quarter of the images (", H, "x", W, "): antialias shrinks by at most 4x");
+  } else {
+    TORCH_CHECK(LH >= H && LW >= W, "augment_pairs: load size ", LH, "x", LW, " is smaller than the images (", H,
+                "x", W, "): only magnification or identity");
+  }
   TORCH_CHECK(CH >= 1 && CH <= LH && CW >= 1 && CW <= LW, "augment_pairs: crop ", CH, "x", CW,
               " does not fit the load size ", LH, "x", LW);
   TORCH_CHECK(2 * LH * (H + 1) <= INT32_MAX && 2 * LW * (W + 1) <= INT32_MAX, "augment_pairs: sizes too large");
+  TORCH_CHECK(!antialias || (2 * LH * H + 5 * std::max(LH, H) <= INT32_MAX && 2 * LW * W + 5 * std::max(LW, W) <= INT32_MAX),
+              "augment_pairs: sizes too large");
   TORCH_CHECK(dtype == 0 || dtype == 1, "augment_pairs: dtype 0 (fp32) or 1 (bf16)");
   TORCH_CHECK(params.scalar_type() == at::kInt && params.dim() == 2 && params.size(1) == 4 && params.is_contiguous(),
               "augment_pairs: params is a contiguous int32 [B, 4] tensor");
@@ -1533,8 +1544,9 @@ std::vector<Tensor> augment_pairs(const Tensor& a, const Tensor& b, const Tensor
   const auto opt = a.options().dtype(dtype == 1 ? at::kBFloat16 : at::kFloat).memory_format(at::MemoryFormat::ChannelsLast);
   Tensor oa = at::empty({B, 3, CH, CW}, opt), ob = at::empty({B, 3, CH, CW}, opt);
   if (B == 0) return {oa, ob};
-  check_rc(p2p_augment_pairs(a.data_ptr(), b.data_ptr(), p.data_ptr<int>(), (int)N, (int)H, (int)W, (int)B, (int)LH,
-                             (int)LW, (int)CH, (int)CW, (int)dtype, oa.data_ptr(), ob.data_ptr(), cur_stream(a)),
+  check_rc((antialias ? p2p_augment_pairs_aa : p2p_augment_pairs)(
+               a.data_ptr(), b.data_ptr(), p.data_ptr<int>(), (int)N, (int)H, (int)W, (int)B, (int)LH, (int)LW, (int)CH,
+               (int)CW, (int)dtype, oa.data_ptr(), ob.data_ptr(), cur_stream(a)),
            "augment_pairs");
   return {oa, ob};
 }
@@ -2108,7 +2120,7 @@ TORCH_LIBRARY(p2p, m) {
   m.def("ssim_loss_fwd(Tensor x, Tensor y, int window, float data_range) -> Tensor");
   m.def("ssim_loss_bwd(Tensor x, Tensor y, int window, float data_range, Tensor gout, bool need_x, "
         "bool need_y) -> Tensor[]");
-  m.def("augment_pairs(Tensor a, Tensor b, Tensor params, int LH, int LW, int CH, int CW, int dtype) -> Tensor[]");
+  m.def("augment_pairs(Tensor a, Tensor b, Tensor params, int LH, int LW, int CH, int CW, int dtype, bool antialias=False) -> Tensor[]");
   m.def("quantize(Tensor x, int bits) -> Tensor");
   m.def("quantize_unshuffle(Tensor x, int bits, int r, int cp) -> Tensor[]");
   m.def("image_metrics(Tensor a, Tensor b, bool shift, float data_range) -> Tensor");

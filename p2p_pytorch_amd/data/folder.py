@@ -61,10 +61,14 @@ class DevicePairCache:
     ``load_size`` (int or (h, w), at least the image size), ``crop_size`` (int or (h, w),
     default the load size) and ``flip`` switch the augmentation on: every epoch draws one
     (y0, x0, flip) per sample next to the permutation, uniform over 0 .. load - crop and
-    {0, 1}.  With all three at their defaults a batch is the plain gather + normalise."""
+    {0, 1}.  With all three at their defaults a batch is the plain gather + normalise.
+    ``antialias`` makes the resize PIL's (and upstream pix2pix's) bicubic, and lets
+    ``load_size`` be smaller than the images, down to a quarter of them; on its own it is not
+    augmentation."""
 
     def __init__(self, dataset: DatasetFromFolder, device, rank: int = 0, world: int = 1,
-                 seed: int = 123, load_size=None, crop_size=None, flip: bool = False):
+                 seed: int = 123, load_size=None, crop_size=None, flip: bool = False,
+                 antialias: bool = False):
         a_list, b_list = [], []
         for name in dataset.image_filenames:
             a_list.append(np.asarray(Image.open(join(dataset.a_path, name)).convert("RGB")))
@@ -88,11 +92,15 @@ class DevicePairCache:
         self._pos = 0
         self.augment = load_size is not None or crop_size is not None or bool(flip)
         self.flip = bool(flip)
+        self.antialias = bool(antialias)
         size = tuple(self.a.shape[1:3])
         self.load = size if load_size is None else self._hw(load_size)
         self.crop = self.load if crop_size is None else self._hw(crop_size)
-        if self.load[0] < size[0] or self.load[1] < size[1]:
-            raise ValueError(f"load_size {self.load} is smaller than the images {size}")
+        if self.antialias:
+            if min(self.load) < 1 or size[0] > 4 * self.load[0] or size[1] > 4 * self.load[1]:
+                raise ValueError(f"load_size {self.load} is less than a quarter of the images {size}")
+        elif self.load[0] < size[0] or self.load[1] < size[1]:
+            raise ValueError(f"load_size {self.load} is smaller than the images {size} (needs antialias)")
         if not (1 <= self.crop[0] <= self.load[0] and 1 <= self.crop[1] <= self.load[1]):
             raise ValueError(f"crop_size {self.crop} does not fit load_size {self.load}")
         self._table = None   # int32 [n, 4] on the device: (index, y0, x0, flip) of this epoch
@@ -137,7 +145,8 @@ class DevicePairCache:
         lo = self._pos + self.rank * batch_size
         self._pos += span
         if self.augment:   # one pass over the cache, one rounding
-            return ops.augment_pairs(self.a, self.b, self._table[lo:lo + batch_size], self.load, self.crop, dtype)
+            return ops.augment_pairs(self.a, self.b, self._table[lo:lo + batch_size], self.load, self.crop, dtype,
+                                     self.antialias)
         idx = self._perm[lo:lo + batch_size]
         return self._to_model(self.a.index_select(0, idx), dtype), self._to_model(
             self.b.index_select(0, idx), dtype)

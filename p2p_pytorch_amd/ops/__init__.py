@@ -161,14 +161,16 @@ def ssim_loss(x, y, window="uniform7", data_range=2.0):
     return ref.ssim_loss(x, y, window, data_range)
 
 
-def augment_pairs(a_u8, b_u8, params, load, crop, dtype=torch.bfloat16):
+def augment_pairs(a_u8, b_u8, params, load, crop, dtype=torch.bfloat16, antialias=False):
     """Random resize / crop / flip of cached uint8 [N, H, W, 3] pairs: per row (index, y0, x0,
     flip) of the int32 table ``params``, image ``index`` resized to ``load`` (bicubic, >= the
     source size), cropped to ``crop`` at (y0, x0), flipped, clamped and scaled to [-1, 1].
+    ``antialias``: the resize is PIL's bicubic (``F.interpolate(antialias=True)``) and ``load``
+    may be smaller than the source, down to a quarter of it.
     Returns two [B, 3, CH, CW] channels_last tensors (see ``reference.augment_pairs``)."""
     if _native.use_native(a_u8):
-        return _hip().augment_pairs(a_u8, b_u8, params, load, crop, dtype)
-    return ref.augment_pairs(a_u8, b_u8, params, load, crop, dtype)
+        return _hip().augment_pairs(a_u8, b_u8, params, load, crop, dtype, antialias)
+    return ref.augment_pairs(a_u8, b_u8, params, load, crop, dtype, antialias)
 
 
 def quantize(x, bits, unshuffle=0):

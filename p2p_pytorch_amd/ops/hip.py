@@ -1865,12 +1865,12 @@ def ssim_loss(x, y, window="uniform7", data_range=2.0):
 AUGMENT_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
 
 
-def augment_pairs(a_u8, b_u8, params, load, crop, dtype=torch.bfloat16):
+def augment_pairs(a_u8, b_u8, params, load, crop, dtype=torch.bfloat16, antialias=False):
     """csrc/augment.hip: one launch from the uint8 cache to the two model-range batches."""
     if dtype not in AUGMENT_DTYPES:
         raise TypeError(f"augment_pairs: bf16 or fp32 output, got {dtype}")
     a, b = P().augment_pairs(a_u8, b_u8, params, int(load[0]), int(load[1]), int(crop[0]), int(crop[1]),
-                             AUGMENT_DTYPES[dtype])
+                             AUGMENT_DTYPES[dtype], bool(antialias))
     return a, b
 
 

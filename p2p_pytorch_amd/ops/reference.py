@@ -161,7 +161,7 @@ def ssim_loss(x: torch.Tensor, y: torch.Tensor, window: str = "uniform7",
 
 
 def augment_pairs(a_u8: torch.Tensor, b_u8: torch.Tensor, params: torch.Tensor, load, crop,
-                  dtype=torch.bfloat16):
+                  dtype=torch.bfloat16, antialias: bool = False):
     """Random resize / crop / flip of cached pairs (the oracle of csrc/augment.hip).
 
     ``a_u8`` / ``b_u8``: uint8 [N, H, W, 3]; ``params``: int [B, 4] rows (index, y0, x0, flip);
@@ -169,11 +169,18 @@ def augment_pairs(a_u8: torch.Tensor, b_u8: torch.Tensor, params: torch.Tensor, 
     ``load`` by ``F.interpolate(mode="bicubic", align_corners=False)`` (skipped when it is the
     source size), cropped at (y0, x0), flipped horizontally when ``flip``, clamped to
     [0, 255] and scaled to [-1, 1].  Math in float32, or float64 when ``dtype`` is float64;
-    returns two [B, 3, CH, CW] channels_last tensors of ``dtype``.
+    returns two [B, 3, CH, CW] channels_last tensors of ``dtype``.  With ``antialias`` the
+    resize is ``F.interpolate(..., antialias=True)`` (PIL's bicubic: Keys a = -0.5, the support
+    stretched by the scale, edge taps cut off and the weights renormalised), also at the source
+    size, and ``load`` may be as small as a quarter of (H, W).
     """
     (LH, LW), (CH, CW) = load, crop
     N, H, W = a_u8.shape[:3]
-    if LH < H or LW < W:
+    if antialias:
+        if LH < 1 or LW < 1 or H > 4 * LH or W > 4 * LW:
+            raise ValueError(f"augment_pairs: load size {LH}x{LW} is less than a quarter of the images ({H}x{W}): "
+                             "antialias shrinks by at most 4x")
+    elif LH < H or LW < W:
         raise ValueError(f"augment_pairs: load size {LH}x{LW} is smaller than the images ({H}x{W})")
     if not (1 <= CH <= LH and 1 <= CW <= LW):
         raise ValueError(f"augment_pairs: crop {CH}x{CW} does not fit the load size {LH}x{LW}")
@@ -186,7 +193,9 @@ def augment_pairs(a_u8: torch.Tensor, b_u8: torch.Tensor, params: torch.Tensor, 
 
     def one(src):
         x = src.index_select(0, index).permute(0, 3, 1, 2).to(compute)
-        if (LH, LW) != (H, W):
+        if antialias:
+            x = F.interpolate(x, size=(LH, LW), mode="bicubic", align_corners=False, antialias=True)
+        elif (LH, LW) != (H, W):
             x = F.interpolate(x, size=(LH, LW), mode="bicubic", align_corners=False)
         out = []
         for n, (_, y0, x0, fl) in enumerate(rows):

@@ -90,6 +90,9 @@ def build_parser():
                         "(0 = the load size, or the image size)")
     p.add_argument("--flip", action="store_true",
                    help="(--device_cache) one random horizontal flip per pair")
+    p.add_argument("--antialias", action="store_true",
+                   help="(--device_cache) resize with PIL's (upstream pix2pix's) antialiased bicubic; "
+                        "needed for a --load_size below the image size (down to a quarter of it)")
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp8"],
                    help="(native) conv GEMM operand precision: bf16, or fp8 (e4m3 fwd / e5m2 dgrad)")
     p.add_argument("--deterministic", action="store_true",
@@ -140,8 +143,8 @@ def main(argv=None):
         raise Exception("No GPU found, please run without --cuda")
     device = pdist.local_device(local_rank) if use_cuda else torch.device("cpu")
     augment = bool(opt.load_size or opt.crop_size or opt.flip)
-    if augment and not (opt.device_cache and use_cuda and not opt.synthetic):
-        raise SystemExit("--load_size / --crop_size / --flip augment the batches of the device cache: "
+    if (augment or opt.antialias) and not (opt.device_cache and use_cuda and not opt.synthetic):
+        raise SystemExit("--load_size / --crop_size / --flip / --antialias augment the batches of the device cache: "
                          "they need --device_cache on a GPU (--cuda) and a --dataset")
     if use_cuda:
         torch.cuda.set_device(device)
@@ -172,7 +175,7 @@ def main(argv=None):
         if opt.device_cache and use_cuda:
             train_src = DevicePairCache(train_set, device, rank, world, seed=opt.seed,
                                         load_size=opt.load_size or None, crop_size=opt.crop_size or None,
-                                        flip=opt.flip)
+                                        flip=opt.flip, antialias=opt.antialias)
         else:
             sampler = (torch.utils.data.distributed.DistributedSampler(
                 train_set, num_replicas=world, rank=rank, shuffle=True, seed=opt.seed)
