@@ -78,6 +78,14 @@ int p2p_ssim_loss_fwd(const void* x, const void* y, int dtype, const long* strid
                       int window, double data_range, float* ws, float* out, hipStream_t st);
 int p2p_ssim_loss_bwd(const void* x, const void* y, int dtype, const long* strides, int N, int C, int H, int W,
                       int window, double data_range, const float* gout, void* dx, hipStream_t st);
+long p2p_ms_ssim_pyr(int N, int C, int H, int W, int M);
+long p2p_ms_ssim_ws(int N, int C, int H, int W, int M);
+int p2p_ms_ssim_fwd(const void* x, const void* y, int dtype, const long* strides, int N, int C, int H, int W,
+                    int window, double data_range, const double* weights, int M, float* pyr, float* ws, float* ms,
+                    float* coef, float* loss, hipStream_t st);
+int p2p_ms_ssim_bwd(const void* x, const void* y, int dtype, const long* strides, int N, int C, int H, int W,
+                    int window, double data_range, int M, const float* pyr, int swap, const float* coef,
+                    const float* gout, float* gtmp, void* dx, hipStream_t st);
 int p2p_augment_pairs(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
                       int CH, int CW, int dtype, void* out_a, void* out_b, hipStream_t st);
 int p2p_augment_pairs_aa(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
@@ -1497,6 +1505,71 @@ std::vector<Tensor> ssim_loss_bwd(const Tensor& x, const Tensor& y, int64_t wind
   return {gx, gy};
 }
 
+// Multi-scale SSIM loss (csrc/ms_ssim_loss.hip): the checks of check_ssim plus the size rule
+// min(H, W) >> (M - 1) >= K (the coarsest of the M scales still holds one window).
+static void check_ms_ssim(const Tensor& x, const Tensor& y, int64_t window, int64_t M, const char* what) {
+  check_ssim(x, y, window, what);
+  TORCH_CHECK(M >= 1 && M <= 5, what, ": 1 to 5 scales, got ", M);
+  const int64_t k = window == 1 ? 11 : 7;
+  TORCH_CHECK((std::min(x.size(2), x.size(3)) >> (M - 1)) >= k, what, ": ", M, " scales with a ", k, "x", k,
+              " window need images of at least ", k << (M - 1), " pixels a side, got ", x.size(2), "x", x.size(3));
+}
+
+// {loss, ms [N, C], pyramid (flat fp32: scales 2 .. M, x then y of each), coef [M, N, C]}
+std::vector<Tensor> ms_ssim_loss_fwd(const Tensor& x, const Tensor& y, int64_t window, double data_range,
+                                     at::ArrayRef<double> weights) {
+  const int M = (int)weights.size();
+  check_ms_ssim(x, y, window, M, "ms_ssim_loss_fwd");
+  const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
+  const long st[8] = {(long)x.stride(0), (long)x.stride(1), (long)x.stride(2), (long)x.stride(3),
+                      (long)y.stride(0), (long)y.stride(1), (long)y.stride(2), (long)y.stride(3)};
+  auto f32 = x.options().dtype(at::kFloat);
+  Tensor pyr = at::empty({p2p_ms_ssim_pyr(N, C, H, W, M)}, f32);
+  Tensor ws = at::empty({p2p_ms_ssim_ws(N, C, H, W, M)}, f32);
+  Tensor ms = at::empty({N, C}, f32), coef = at::empty({M, N, C}, f32), loss = at::empty({}, f32);
+  check_rc(p2p_ms_ssim_fwd(x.data_ptr(), y.data_ptr(), x.scalar_type() == at::kBFloat16 ? 1 : 0, st, N, C, H, W,
+                           (int)window, data_range, weights.data(), M, pyr.data_ptr<float>(), ws.data_ptr<float>(),
+                           ms.data_ptr<float>(), coef.data_ptr<float>(), loss.data_ptr<float>(), cur_stream(x)),
+           "ms_ssim_loss_fwd");
+  return {loss, ms, pyr, coef};
+}
+
+// {dL/dx, dL/dy} (undefined where not needed), each laid out like its image
+std::vector<Tensor> ms_ssim_loss_bwd(const Tensor& x, const Tensor& y, const Tensor& pyr, const Tensor& coef,
+                                     int64_t window, double data_range, const Tensor& gout, bool need_x,
+                                     bool need_y) {
+  TORCH_CHECK(coef.dim() == 3, "ms_ssim_loss_bwd: coef [M, N, C]");
+  const int M = (int)coef.size(0);
+  check_ms_ssim(x, y, window, M, "ms_ssim_loss_bwd");
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "ms_ssim_loss_bwd: gout");
+  const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
+  TORCH_CHECK(pyr.is_cuda() && pyr.scalar_type() == at::kFloat && pyr.is_contiguous() &&
+                  pyr.numel() == p2p_ms_ssim_pyr(N, C, H, W, M),
+              "ms_ssim_loss_bwd: the pyramid of this forward");
+  TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.size(1) == N &&
+                  coef.size(2) == C,
+              "ms_ssim_loss_bwd: the coefficients of this forward");
+  Tensor g = gout.contiguous();
+  const int dt = x.scalar_type() == at::kBFloat16 ? 1 : 0;
+  // gradients of the coarser scales (fp32, half the pyramid): dead after the call
+  Tensor gtmp = at::empty({pyr.numel() / 2}, pyr.options());
+  auto run = [&](const Tensor& a, const Tensor& b, int swap) {
+    Tensor d = at::empty_like(a);
+    const long st[12] = {(long)a.stride(0), (long)a.stride(1), (long)a.stride(2), (long)a.stride(3),
+                         (long)b.stride(0), (long)b.stride(1), (long)b.stride(2), (long)b.stride(3),
+                         (long)d.stride(0), (long)d.stride(1), (long)d.stride(2), (long)d.stride(3)};
+    check_rc(p2p_ms_ssim_bwd(a.data_ptr(), b.data_ptr(), dt, st, N, C, H, W, (int)window, data_range, M,
+                             pyr.data_ptr<float>(), swap, coef.data_ptr<float>(), g.data_ptr<float>(),
+                             gtmp.data_ptr<float>(), d.data_ptr(), cur_stream(a)),
+             "ms_ssim_loss_bwd");
+    return d;
+  };
+  Tensor gx, gy;
+  if (need_x) gx = run(x, y, 0);
+  if (need_y) gy = run(y, x, 1);
+  return {gx, gy};
+}
+
 // Random resize / crop / flip of cached pairs (csrc/augment.hip).  a, b: the uint8 [N, H, W, 3]
 // cache; params: int32 [B, 4] rows (index, y0, x0, flip).  A CPU table is range-checked here
 // and copied up; a device table is trusted (the kernel clamps each row into range, so a bad
@@ -2120,6 +2193,9 @@ TORCH_LIBRARY(p2p, m) {
   m.def("ssim_loss_fwd(Tensor x, Tensor y, int window, float data_range) -> Tensor");
   m.def("ssim_loss_bwd(Tensor x, Tensor y, int window, float data_range, Tensor gout, bool need_x, "
         "bool need_y) -> Tensor[]");
+  m.def("ms_ssim_loss_fwd(Tensor x, Tensor y, int window, float data_range, float[] weights) -> Tensor[]");
+  m.def("ms_ssim_loss_bwd(Tensor x, Tensor y, Tensor pyr, Tensor coef, int window, float data_range, Tensor gout, "
+        "bool need_x, bool need_y) -> Tensor[]");
   m.def("augment_pairs(Tensor a, Tensor b, Tensor params, int LH, int LW, int CH, int CW, int dtype, bool antialias=False) -> Tensor[]");
   m.def("quantize(Tensor x, int bits) -> Tensor");
   m.def("quantize_unshuffle(Tensor x, int bits, int r, int cp) -> Tensor[]");
@@ -2198,6 +2274,8 @@ TORCH_LIBRARY_IMPL(p2p, CUDA, m) {
   m.impl("tv_bwd", tv_bwd);
   m.impl("ssim_loss_fwd", ssim_loss_fwd);
   m.impl("ssim_loss_bwd", ssim_loss_bwd);
+  m.impl("ms_ssim_loss_fwd", ms_ssim_loss_fwd);
+  m.impl("ms_ssim_loss_bwd", ms_ssim_loss_bwd);
   m.impl("augment_pairs", augment_pairs);
   m.impl("quantize", quantize);
   m.impl("quantize_unshuffle", quantize_unshuffle);

@@ -65,7 +65,7 @@ class CompressGANStep:
                  lambda_vgg=10.0, lambda_tv=1.0, n_layers_d=3, num_d=3, image_pool=None,
                  train_c=False, c_phase_backward=False, vgg=None, reducer_g=None,
                  reducer_d=None, reducer_c=None, nan_guard=True, lambda_ssim=0.0,
-                 ssim_window="uniform7"):
+                 ssim_window="uniform7", lambda_msssim=0.0, msssim_scales=5):
         self.net_g, self.net_d, self.net_c = net_g, net_d, net_c
         self.criterionGAN = GANLoss()                      # LSGAN, reference default
         self.criterionVGG = vgg if vgg is not None else VGGLoss()
@@ -75,6 +75,10 @@ class CompressGANStep:
         self.lambda_feat, self.lambda_vgg, self.lambda_tv = lambda_feat, lambda_vgg, lambda_tv
         # optional structural term lambda_ssim * (1 - SSIM(fake_b, real_b)); 0 = not built
         self.lambda_ssim, self.ssim_window = float(lambda_ssim), ssim_window
+        # optional multi-scale term lambda_msssim * (1 - MS-SSIM(fake_b, real_b)) over the first
+        # msssim_scales of the five weights (renormalised), same window; 0 = not built
+        self.lambda_msssim = float(lambda_msssim)
+        self.msssim_weights = ops.ms_ssim_weights(msssim_scales)
         self.feat_weights = 4.0 / (n_layers_d + 1)
         self.d_weights = 1.0 / num_d
         self.opt_g = make_adam(net_g.parameters(), lr=lr, betas=(beta1, 0.999))
@@ -167,6 +171,8 @@ class CompressGANStep:
 
     def step(self, real_a, real_b):
         G, D, C = self.net_g, self.net_d, self.net_c
+        if self.lambda_msssim > 0:    # the size rule, before any work of the step
+            ops.ms_ssim_check(real_b.shape, self.ssim_window, len(self.msssim_weights), "lambda_msssim")
         if real_a.is_cuda and _native.get_backend() == "native":
             from ..ops import hip
             hip.begin_step()
@@ -190,7 +196,8 @@ class CompressGANStep:
         set_requires_grad(self._d_trainable, False)
         # fake_b feeds D, VGG and TV: one fan-out node sums their gradients with HIP adds
         use_ssim = self.lambda_ssim > 0
-        fake_d, fake_v, fake_t, *fake_s = ops.fan_out(fake_b, 4 if use_ssim else 3)
+        use_msssim = self.lambda_msssim > 0
+        fake_d, fake_v, fake_t, *fake_s = ops.fan_out(fake_b, 3 + use_ssim + use_msssim)
         pred_fake_g = D(self._d_in(real_a, fake_d))
         # back on before any backward: autograd's AccumulateGrad skips a leaf that no longer
         # requires grad, which would silently drop the D-loss gradients
@@ -219,11 +226,15 @@ class CompressGANStep:
         vgg_g = self._vgg(fake_v, real_b, fy_real)
         tv = calc_tv_Loss(fake_t)
         ssim = ops.ssim_loss(fake_s[0], real_b, self.ssim_window) if use_ssim else None
+        msssim = (ops.ms_ssim_loss(fake_s[-1], real_b, self.ssim_window, weights=self.msssim_weights)
+                  if use_msssim else None)
         if native:
             terms = [loss_g_gan] + ([loss_feat] if feat else []) + [vgg_g, tv]
             weights = [1.0] + ([1.0] if feat else []) + [self.lambda_vgg, self.lambda_tv]
             if use_ssim:
                 terms, weights = terms + [ssim], weights + [self.lambda_ssim]
+            if use_msssim:
+                terms, weights = terms + [msssim], weights + [self.lambda_msssim]
             loss_g = ops.lincomb_n(terms, weights)
             with torch.no_grad():
                 content = ops.lincomb_n([vgg_g.detach()], [self.lambda_vgg])
@@ -232,6 +243,8 @@ class CompressGANStep:
             loss_g = loss_g_gan + loss_feat + content + tv * self.lambda_tv
             if use_ssim:
                 loss_g = loss_g + ssim * self.lambda_ssim
+            if use_msssim:
+                loss_g = loss_g + msssim * self.lambda_msssim
         # ---- updates: G first (its backward also reaches D; those grads are dropped)
         with self._phase("G_bwd_opt"):
             self._zero(self.opt_g, self.reducer_g)
@@ -278,4 +291,6 @@ class CompressGANStep:
                "VGG": content.detach(), "TV": tv.detach(), "G": loss_g.detach()}
         if use_ssim:
             out["SSIM"] = ssim.detach()
+        if use_msssim:
+            out["MSSSIM"] = msssim.detach()
         return out

@@ -68,6 +68,19 @@ class SSIMLoss(nn.Module):
         return ops.ssim_loss(pred, target, self.window, self.data_range)
 
 
+class MSSSIMLoss(nn.Module):
+    """1 - mean MS-SSIM(pred, target) on model-range images (``ops.ms_ssim_loss``) over the
+    first ``scales`` of the five standard weights, renormalised to sum 1."""
+
+    def __init__(self, window="gauss11", data_range=2.0, scales=5):
+        super().__init__()
+        self.window, self.data_range = window, float(data_range)
+        self.weights = ops.ms_ssim_weights(scales)
+
+    def forward(self, pred, target):
+        return ops.ms_ssim_loss(pred, target, self.window, self.data_range, self.weights)
+
+
 class angular_loss(nn.Module):
     """mean(acos(clamp(cos_sim_c(a, b)))) in degrees (networks.py:870-894)."""
 

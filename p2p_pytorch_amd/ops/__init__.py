@@ -161,6 +161,28 @@ def ssim_loss(x, y, window="uniform7", data_range=2.0):
     return ref.ssim_loss(x, y, window, data_range)
 
 
+MS_SSIM_WEIGHTS = ref.MS_SSIM_WEIGHTS
+ms_ssim_weights = ref.ms_ssim_weights
+ms_ssim_check = ref.ms_ssim_check
+
+
+def ms_ssim_loss(x, y, window="gauss11", data_range=2.0, weights=MS_SSIM_WEIGHTS):
+    """1 - mean over n, c of the multi-scale SSIM of two [N, C, H, W] images over
+    ``len(weights)`` scales, differentiable in both (see ``reference.ms_ssim``).  Needs
+    ``min(H, W) >> (len(weights) - 1)`` >= the window size."""
+    if _native.use_native(x):
+        return _hip().ms_ssim_loss(x, y, window, data_range, weights)
+    return ref.ms_ssim_loss(x, y, window, data_range, weights)
+
+
+def ms_ssim(x, y, window="gauss11", data_range=2.0, weights=MS_SSIM_WEIGHTS):
+    """The [N, C] multi-scale SSIM values of ``ms_ssim_loss``'s forward, without a graph."""
+    if _native.use_native(x):
+        return _hip().ms_ssim(x, y, window, data_range, weights)
+    with torch.no_grad():
+        return ref.ms_ssim(x, y, window, data_range, weights)
+
+
 def augment_pairs(a_u8, b_u8, params, load, crop, dtype=torch.bfloat16, antialias=False):
     """Random resize / crop / flip of cached uint8 [N, H, W, 3] pairs: per row (index, y0, x0,
     flip) of the int32 table ``params``, image ``index`` resized to ``load`` (bicubic, >= the

@@ -1862,6 +1862,52 @@ def ssim_loss(x, y, window="uniform7", data_range=2.0):
     return SSIMLossFn.apply(x, y, SSIM_WINDOWS[window], float(data_range))
 
 
+class MSSSIMLossFn(torch.autograd.Function):
+    """1 - mean MS-SSIM (csrc/ms_ssim_loss.hip).  Saves the two images, the fp32 pyramid of
+    their pooled scales (2 x 1/3 of the pixels) and the [M, N, C] backward coefficients; the
+    backward kernels recompute the window moments, so no per-origin map is kept.  Also
+    returns the per-(n, c) values (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, x, y, window, data_range, weights):
+        if y.dtype != x.dtype:
+            y = y.to(x.dtype)
+        loss, ms, pyr, coef = P().ms_ssim_loss_fwd(x, y, window, data_range, weights)
+        ctx.window, ctx.data_range = window, data_range
+        ctx.save_for_backward(x, y, pyr, coef)
+        ctx.mark_non_differentiable(ms)
+        return loss, ms
+
+    @staticmethod
+    def backward(ctx, gout, _gms):
+        x, y, pyr, coef = ctx.saved_tensors
+        nx, ny = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx, gy = P().ms_ssim_loss_bwd(x, y, pyr, coef, ctx.window, ctx.data_range, gout.float().reshape(1),
+                                      nx, ny)
+        return (gx if nx else None), (gy if ny else None), None, None, None
+
+
+def _ms_ssim(x, y, window, data_range, weights):
+    from . import reference as ref
+    if window not in SSIM_WINDOWS:
+        raise ValueError(f"ms_ssim_loss: unknown window {window!r} (uniform7 | gauss11)")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"ms_ssim_loss: fp32 or bf16 images, got {x.dtype}")   # no silent upcast
+    ref.ms_ssim_check(x.shape, window, len(weights))
+    return MSSSIMLossFn.apply(x, y, SSIM_WINDOWS[window], float(data_range), [float(w) for w in weights])
+
+
+def ms_ssim_loss(x, y, window="gauss11", data_range=2.0, weights=None):
+    from . import reference as ref
+    return _ms_ssim(x, y, window, data_range, ref.MS_SSIM_WEIGHTS if weights is None else weights)[0]
+
+
+def ms_ssim(x, y, window="gauss11", data_range=2.0, weights=None):
+    from . import reference as ref
+    with torch.no_grad():
+        return _ms_ssim(x, y, window, data_range, ref.MS_SSIM_WEIGHTS if weights is None else weights)[1]
+
+
 AUGMENT_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
 
 

@@ -160,6 +160,77 @@ def ssim_loss(x: torch.Tensor, y: torch.Tensor, window: str = "uniform7",
     return 1.0 - s.mean()
 
 
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)     # Wang et al. 2003
+
+
+def ms_ssim_weights(scales: int):
+    """The first ``scales`` of the five MS-SSIM weights, renormalised to sum 1."""
+    if not 1 <= scales <= len(MS_SSIM_WEIGHTS):
+        raise ValueError(f"ms_ssim: 1 to {len(MS_SSIM_WEIGHTS)} scales, got {scales}")
+    w = MS_SSIM_WEIGHTS[:scales]
+    return tuple(v / sum(w) for v in w)
+
+
+def ms_ssim_check(shape, window: str, scales: int, what: str = "ms_ssim_loss"):
+    """The size rule ``min(H, W) >> (M - 1) >= K``: the coarsest scale still holds one window."""
+    k = ssim_window(window)[0].numel()
+    if not 1 <= scales <= len(MS_SSIM_WEIGHTS):
+        raise ValueError(f"{what}: 1 to {len(MS_SSIM_WEIGHTS)} scales, got {scales}")
+    if (min(shape[-2:]) >> (scales - 1)) < k:
+        raise ValueError(f"{what}: {scales} scales with the {window} window need images of at least "
+                         f"{k << (scales - 1)} pixels a side, got {shape[-2]}x{shape[-1]}")
+
+
+def ms_ssim(x: torch.Tensor, y: torch.Tensor, window: str = "gauss11", data_range: float = 2.0,
+            weights=MS_SSIM_WEIGHTS) -> torch.Tensor:
+    """Multi-scale SSIM per image and channel, [N, C]: ``prod_j f_j ** w_j``.
+
+    Scale 1 is the input, scale j + 1 is ``F.avg_pool2d(., 2)`` of scale j (a trailing odd row
+    or column is dropped).  With ``M = len(weights)``, ``f_j`` for j < M is the mean over the
+    valid window origins of the contrast-structure term ``cs = A2 / B2`` and ``f_M`` the mean
+    of the full SSIM; windows, covariance factor, C1 / C2 and the continuous model-range
+    semantics are those of ``ssim_loss``.  An (n, c) with any ``f_j <= 0`` has the value 0 and
+    contributes an exactly zero gradient (masks, not a clamp: ``clamp_min(0) ** w`` has the
+    backward 0 * inf).  Keeps the dtype it is given (half types go to fp32).
+    """
+    if x.dtype in (torch.bfloat16, torch.float16):
+        x = x.float()
+    y = y.to(x.dtype)
+    M = len(weights)
+    ms_ssim_check(x.shape, window, M)
+    g, f = ssim_window(window, x.dtype, x.device)
+    C, k = x.shape[1], g.numel()
+    w = (g[:, None] * g[None, :]).expand(C, 1, k, k).contiguous()
+    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+
+    def E(t):
+        return F.conv2d(t, w, groups=C)
+
+    fs = []
+    for j in range(M):
+        ux, uy = E(x), E(y)
+        vx = f * (E(x * x) - ux * ux)
+        vy = f * (E(y * y) - uy * uy)
+        vxy = f * (E(x * y) - ux * uy)
+        s = (2 * vxy + c2) / (vx + vy + c2)
+        if j == M - 1:
+            s = s * (2 * ux * uy + c1) / (ux * ux + uy * uy + c1)
+        else:
+            x, y = F.avg_pool2d(x, 2), F.avg_pool2d(y, 2)
+        fs.append(s.mean(dim=(2, 3)))
+    fs = torch.stack(fs)                                            # [M, N, C]
+    ok = (fs > 0).all(dim=0)
+    wt = torch.tensor(weights, dtype=x.dtype, device=x.device)[:, None, None]
+    ms = (torch.where(ok, fs, torch.ones_like(fs)) ** wt).prod(dim=0)
+    return torch.where(ok, ms, torch.zeros_like(ms))
+
+
+def ms_ssim_loss(x: torch.Tensor, y: torch.Tensor, window: str = "gauss11", data_range: float = 2.0,
+                 weights=MS_SSIM_WEIGHTS) -> torch.Tensor:
+    """1 - mean over n, c of ``ms_ssim`` (the oracle of csrc/ms_ssim_loss.hip)."""
+    return 1.0 - ms_ssim(x, y, window, data_range, weights).mean()
+
+
 def augment_pairs(a_u8: torch.Tensor, b_u8: torch.Tensor, params: torch.Tensor, load, crop,
                   dtype=torch.bfloat16, antialias: bool = False):
     """Random resize / crop / flip of cached pairs (the oracle of csrc/augment.hip).

@@ -68,6 +68,12 @@ def build_parser():
                    help="weight on the SSIM loss term 1 - SSIM(fake, real) of the G objective (0 = off)")
     p.add_argument("--ssim_window", default="uniform7", choices=["uniform7", "gauss11"],
                    help="SSIM loss window: 7x7 box (the printed metric's) or 11x11 Gaussian")
+    p.add_argument("--lambda_msssim", type=float, default=0.0,
+                   help="weight on the multi-scale term 1 - MS-SSIM(fake, real) of the G objective (0 = off); "
+                        "its window is --ssim_window")
+    p.add_argument("--msssim_scales", type=int, default=5, choices=[1, 2, 3, 4, 5],
+                   help="MS-SSIM scales: the first M of the five weights, renormalised; the images need "
+                        "min(H, W) >> (M - 1) >= the window size")
     # ---- new
     p.add_argument("--netG", default="expand", help="expand | unet_256 | unet_128 | unet_<levels>")
     p.add_argument("--netD", default=None, help="multiscale | basic | n_layers | pixel")
@@ -221,7 +227,8 @@ def main(argv=None):
                               reducer_g=reducer_g, reducer_d=reducer_d,
                               autocast_dtype=torch.bfloat16 if (use_cuda and p2p.get_backend() == "torch") else None,
                               nan_guard=not opt.no_nan_guard,
-                              lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window)
+                              lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window,
+                              lambda_msssim=opt.lambda_msssim, msssim_scales=opt.msssim_scales)
         opt_g, opt_d = trainer.opt_G, trainer.opt_D
     else:
         from p2p_pytorch_amd.engine.compress_gan import CompressGANStep
@@ -231,7 +238,8 @@ def main(argv=None):
                                   train_c=opt.train_c, c_phase_backward=opt.c_phase_backward,
                                   reducer_g=reducer_g, reducer_d=reducer_d, reducer_c=reducer_c,
                                   nan_guard=not opt.no_nan_guard,
-                                  lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window)
+                                  lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window,
+                                  lambda_msssim=opt.lambda_msssim, msssim_scales=opt.msssim_scales)
         opt_g, opt_d = trainer.opt_g, trainer.opt_d
     # the reference's third optimizer / scheduler pair (train.py:243-246, :441-443): over C
     # when --train_c fixes quirk A1, and stepped + checkpointed like the other two
