@@ -16,6 +16,8 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
+#include <mutex>
 #include <vector>
 
 #include "conv.h"
@@ -86,6 +88,15 @@ int p2p_ms_ssim_fwd(const void* x, const void* y, int dtype, const long* strides
 int p2p_ms_ssim_bwd(const void* x, const void* y, int dtype, const long* strides, int N, int C, int H, int W,
                     int window, double data_range, int M, const float* pyr, int swap, const float* coef,
                     const float* gout, float* gtmp, void* dx, hipStream_t st);
+long p2p_ffl_spec(int N, int C, int H, int W);
+long p2p_ffl_ws(int N, int C, int H, int W);
+int p2p_ffl_fwd(const void* x, const void* y, int dtype, const long* strides, int N, int C, int H, int W,
+                double alpha, const float* twh, const float* tww, float* z, float* f, float* ws, float* inv,
+                float* loss, hipStream_t st);
+int p2p_ffl_bwd(const float* f, const float* inv, const float* gout, int dtype, const long* strides, int N, int C,
+                int H, int W, double alpha, const float* twh, const float* tww, float* ysc, void* dx, void* dy,
+                hipStream_t st);
+void p2p_ffl_twiddles(int n, float* out);
 int p2p_augment_pairs(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
                       int CH, int CW, int dtype, void* out_a, void* out_b, hipStream_t st);
 int p2p_augment_pairs_aa(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
@@ -1570,6 +1581,88 @@ std::vector<Tensor> ms_ssim_loss_bwd(const Tensor& x, const Tensor& y, const Ten
   return {gx, gy};
 }
 
+// Focal frequency loss (csrc/ffl_loss.hip).  Size rule: H and W each a multiple of 32 in
+// [32, 512].
+static void check_ffl_size(int64_t H, int64_t W, const char* what) {
+  auto ok = [](int64_t n) { return n >= 32 && n <= 512 && n % 32 == 0; };
+  TORCH_CHECK_VALUE(ok(H) && ok(W), what, ": H and W must each be a multiple of 32 in [32, 512], got ", H, "x", W);
+}
+
+// The [2, n, n] twiddle pair (cos, sin of 2 pi (k j mod n) / n, over sqrt(n)) of one transform
+// length on one device: built once on the host in float64 and kept for the process, so the
+// pair of any (H, W, device) is cached after its first use.  The first use copies from the
+// host: warm a size up before capturing it into a graph.
+static Tensor ffl_twiddles(int64_t n, const at::Device& dev) {
+  static std::mutex mu;
+  static std::map<std::pair<int64_t, int>, Tensor> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  const auto key = std::make_pair(n, (int)dev.index());
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  Tensor host = at::empty({2, n, n}, at::TensorOptions().dtype(at::kFloat));
+  p2p_ffl_twiddles((int)n, host.data_ptr<float>());
+  Tensor t = host.to(dev);
+  cache.emplace(key, t);
+  return t;
+}
+
+// {loss, F (the half spectrum, fp32 [N, C, 2, H, W / 2 + 1]), inv [N, C]}: all the backward needs
+std::vector<Tensor> ffl_loss_fwd(const Tensor& x, const Tensor& y, double alpha) {
+  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.dim() == 4 && x.sizes() == y.sizes(),
+              "ffl_loss_fwd: two 4-D CUDA tensors of one shape");
+  TORCH_CHECK(x.scalar_type() == y.scalar_type() &&
+                  (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
+              "ffl_loss_fwd: fp32 or bf16 inputs of one dtype");
+  TORCH_CHECK(alpha >= 0.0, "ffl_loss_fwd: alpha >= 0");
+  check_ffl_size(x.size(2), x.size(3), "ffl_loss_fwd");
+  TORCH_CHECK(x.size(0) >= 1 && x.size(1) >= 1 && x.size(0) * x.size(1) < (1 << 26), "ffl_loss_fwd: N * C");
+  const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
+  const long st[8] = {(long)x.stride(0), (long)x.stride(1), (long)x.stride(2), (long)x.stride(3),
+                      (long)y.stride(0), (long)y.stride(1), (long)y.stride(2), (long)y.stride(3)};
+  auto f32 = x.options().dtype(at::kFloat);
+  Tensor twh = ffl_twiddles(H, x.device()), tww = ffl_twiddles(W, x.device());
+  Tensor z = at::empty({p2p_ffl_spec(N, C, H, W)}, f32);   // scratch: dead on return
+  Tensor f = at::empty({N, C, 2, H, W / 2 + 1}, f32);
+  Tensor ws = at::empty({p2p_ffl_ws(N, C, H, W)}, f32);
+  Tensor inv = at::empty({N, C}, f32), loss = at::empty({}, f32);
+  check_rc(p2p_ffl_fwd(x.data_ptr(), y.data_ptr(), x.scalar_type() == at::kBFloat16 ? 1 : 0, st, N, C, H, W, alpha,
+                       twh.data_ptr<float>(), tww.data_ptr<float>(), z.data_ptr<float>(), f.data_ptr<float>(),
+                       ws.data_ptr<float>(), inv.data_ptr<float>(), loss.data_ptr<float>(), cur_stream(x)),
+           "ffl_loss_fwd");
+  return {loss, f, inv};
+}
+
+// {dL/dx, dL/dy} (dy undefined unless need_y), allocated with the given strides (those of a
+// tensor like the image) and dtype (0 = fp32, 1 = bf16): the images themselves are not kept
+std::vector<Tensor> ffl_loss_bwd(const Tensor& f, const Tensor& inv, const Tensor& gout, at::IntArrayRef strides,
+                                 int64_t dtype, double alpha, bool need_y) {
+  TORCH_CHECK(f.is_cuda() && f.scalar_type() == at::kFloat && f.is_contiguous() && f.dim() == 5 && f.size(2) == 2,
+              "ffl_loss_bwd: the spectrum of this forward");
+  const int64_t H = f.size(3), W = 2 * (f.size(4) - 1);
+  check_ffl_size(H, W, "ffl_loss_bwd");
+  const int N = (int)f.size(0), C = (int)f.size(1);
+  TORCH_CHECK(inv.is_cuda() && inv.scalar_type() == at::kFloat && inv.is_contiguous() && inv.dim() == 2 &&
+                  inv.size(0) == N && inv.size(1) == C,
+              "ffl_loss_bwd: the per-plane scales of this forward");
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "ffl_loss_bwd: gout");
+  TORCH_CHECK(strides.size() == 4 && (dtype == 0 || dtype == 1), "ffl_loss_bwd: 4 strides, dtype 0 | 1");
+  Tensor g = gout.contiguous();
+  auto opt = f.options().dtype(dtype == 1 ? at::kBFloat16 : at::kFloat);
+  Tensor dx = at::empty_strided({N, C, H, W}, strides, opt);
+  TORCH_CHECK(dx.is_non_overlapping_and_dense(), "ffl_loss_bwd: dense gradient strides");
+  Tensor dy;
+  if (need_y) dy = at::empty_strided({N, C, H, W}, strides, opt);
+  const long st[8] = {(long)strides[0], (long)strides[1], (long)strides[2], (long)strides[3],
+                      (long)strides[0], (long)strides[1], (long)strides[2], (long)strides[3]};
+  Tensor twh = ffl_twiddles(H, f.device()), tww = ffl_twiddles(W, f.device());
+  Tensor ysc = at::empty({f.numel()}, f.options());   // scratch: dead on return
+  check_rc(p2p_ffl_bwd(f.data_ptr<float>(), inv.data_ptr<float>(), g.data_ptr<float>(), (int)dtype, st, N, C, (int)H,
+                       (int)W, alpha, twh.data_ptr<float>(), tww.data_ptr<float>(), ysc.data_ptr<float>(),
+                       dx.data_ptr(), need_y ? dy.data_ptr() : nullptr, cur_stream(f)),
+           "ffl_loss_bwd");
+  return {dx, dy};
+}
+
 // Random resize / crop / flip of cached pairs (csrc/augment.hip).  a, b: the uint8 [N, H, W, 3]
 // cache; params: int32 [B, 4] rows (index, y0, x0, flip).  A CPU table is range-checked here
 // and copied up; a device table is trusted (the kernel clamps each row into range, so a bad
@@ -2196,6 +2289,8 @@ TORCH_LIBRARY(p2p, m) {
   m.def("ms_ssim_loss_fwd(Tensor x, Tensor y, int window, float data_range, float[] weights) -> Tensor[]");
   m.def("ms_ssim_loss_bwd(Tensor x, Tensor y, Tensor pyr, Tensor coef, int window, float data_range, Tensor gout, "
         "bool need_x, bool need_y) -> Tensor[]");
+  m.def("ffl_loss_fwd(Tensor x, Tensor y, float alpha) -> Tensor[]");
+  m.def("ffl_loss_bwd(Tensor f, Tensor inv, Tensor gout, int[] strides, int dtype, float alpha, bool need_y) -> Tensor[]");
   m.def("augment_pairs(Tensor a, Tensor b, Tensor params, int LH, int LW, int CH, int CW, int dtype, bool antialias=False) -> Tensor[]");
   m.def("quantize(Tensor x, int bits) -> Tensor");
   m.def("quantize_unshuffle(Tensor x, int bits, int r, int cp) -> Tensor[]");
@@ -2276,6 +2371,8 @@ TORCH_LIBRARY_IMPL(p2p, CUDA, m) {
   m.impl("ssim_loss_bwd", ssim_loss_bwd);
   m.impl("ms_ssim_loss_fwd", ms_ssim_loss_fwd);
   m.impl("ms_ssim_loss_bwd", ms_ssim_loss_bwd);
+  m.impl("ffl_loss_fwd", ffl_loss_fwd);
+  m.impl("ffl_loss_bwd", ffl_loss_bwd);
   m.impl("augment_pairs", augment_pairs);
   m.impl("quantize", quantize);
   m.impl("quantize_unshuffle", quantize_unshuffle);

@@ -65,7 +65,8 @@ class CompressGANStep:
                  lambda_vgg=10.0, lambda_tv=1.0, n_layers_d=3, num_d=3, image_pool=None,
                  train_c=False, c_phase_backward=False, vgg=None, reducer_g=None,
                  reducer_d=None, reducer_c=None, nan_guard=True, lambda_ssim=0.0,
-                 ssim_window="uniform7", lambda_msssim=0.0, msssim_scales=5):
+                 ssim_window="uniform7", lambda_msssim=0.0, msssim_scales=5, lambda_ffl=0.0,
+                 ffl_alpha=1.0):
         self.net_g, self.net_d, self.net_c = net_g, net_d, net_c
         self.criterionGAN = GANLoss()                      # LSGAN, reference default
         self.criterionVGG = vgg if vgg is not None else VGGLoss()
@@ -79,6 +80,8 @@ class CompressGANStep:
         # msssim_scales of the five weights (renormalised), same window; 0 = not built
         self.lambda_msssim = float(lambda_msssim)
         self.msssim_weights = ops.ms_ssim_weights(msssim_scales)
+        # optional frequency term lambda_ffl * FFL(fake_b, real_b) (focal frequency loss); 0 = not built
+        self.lambda_ffl, self.ffl_alpha = float(lambda_ffl), float(ffl_alpha)
         self.feat_weights = 4.0 / (n_layers_d + 1)
         self.d_weights = 1.0 / num_d
         self.opt_g = make_adam(net_g.parameters(), lr=lr, betas=(beta1, 0.999))
@@ -173,6 +176,8 @@ class CompressGANStep:
         G, D, C = self.net_g, self.net_d, self.net_c
         if self.lambda_msssim > 0:    # the size rule, before any work of the step
             ops.ms_ssim_check(real_b.shape, self.ssim_window, len(self.msssim_weights), "lambda_msssim")
+        if self.lambda_ffl > 0:
+            ops.ffl_check(real_b.shape, "lambda_ffl")
         if real_a.is_cuda and _native.get_backend() == "native":
             from ..ops import hip
             hip.begin_step()
@@ -197,7 +202,8 @@ class CompressGANStep:
         # fake_b feeds D, VGG and TV: one fan-out node sums their gradients with HIP adds
         use_ssim = self.lambda_ssim > 0
         use_msssim = self.lambda_msssim > 0
-        fake_d, fake_v, fake_t, *fake_s = ops.fan_out(fake_b, 3 + use_ssim + use_msssim)
+        use_ffl = self.lambda_ffl > 0
+        fake_d, fake_v, fake_t, *fake_s = ops.fan_out(fake_b, 3 + use_ssim + use_msssim + use_ffl)
         pred_fake_g = D(self._d_in(real_a, fake_d))
         # back on before any backward: autograd's AccumulateGrad skips a leaf that no longer
         # requires grad, which would silently drop the D-loss gradients
@@ -226,6 +232,7 @@ class CompressGANStep:
         vgg_g = self._vgg(fake_v, real_b, fy_real)
         tv = calc_tv_Loss(fake_t)
         ssim = ops.ssim_loss(fake_s[0], real_b, self.ssim_window) if use_ssim else None
+        ffl = ops.ffl_loss(fake_s.pop(), real_b, self.ffl_alpha) if use_ffl else None
         msssim = (ops.ms_ssim_loss(fake_s[-1], real_b, self.ssim_window, weights=self.msssim_weights)
                   if use_msssim else None)
         if native:
@@ -235,6 +242,8 @@ class CompressGANStep:
                 terms, weights = terms + [ssim], weights + [self.lambda_ssim]
             if use_msssim:
                 terms, weights = terms + [msssim], weights + [self.lambda_msssim]
+            if use_ffl:
+                terms, weights = terms + [ffl], weights + [self.lambda_ffl]
             loss_g = ops.lincomb_n(terms, weights)
             with torch.no_grad():
                 content = ops.lincomb_n([vgg_g.detach()], [self.lambda_vgg])
@@ -245,6 +254,8 @@ class CompressGANStep:
                 loss_g = loss_g + ssim * self.lambda_ssim
             if use_msssim:
                 loss_g = loss_g + msssim * self.lambda_msssim
+            if use_ffl:
+                loss_g = loss_g + ffl * self.lambda_ffl
         # ---- updates: G first (its backward also reaches D; those grads are dropped)
         with self._phase("G_bwd_opt"):
             self._zero(self.opt_g, self.reducer_g)
@@ -293,4 +304,6 @@ class CompressGANStep:
             out["SSIM"] = ssim.detach()
         if use_msssim:
             out["MSSSIM"] = msssim.detach()
+        if use_ffl:
+            out["FFL"] = ffl.detach()
         return out

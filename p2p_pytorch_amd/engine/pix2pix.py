@@ -9,7 +9,7 @@ backward -- SURVEY.md section 5.8):
   3. G phase (D params frozen, so D only back-propagates to its input):
      ``D(cat(A, fake_B))`` vs real label + ``lambda_L1 * |fake_B - B|`` (+ ``lambda_ssim *
      (1 - SSIM(fake_B, B))`` and ``lambda_msssim * (1 - MS-SSIM(fake_B, B))`` when those
-     weights are set) -> backward -> all-reduce G grads -> Adam(G)
+     weights are set, ``lambda_ffl * FFL(fake_B, B)`` likewise) -> backward -> all-reduce G grads -> Adam(G)
 
 The concat of (A, fake_B) is a *virtual* concat on the native path: D's first conv reads
 the two images through two base pointers (``ops.conv2d`` accepts a tuple input).
@@ -25,7 +25,7 @@ from .. import _native
 from ..models.compress_gan import MultiscaleDiscriminator
 from ..models.layers import BatchNorm2d
 from ..models.losses import GANLoss
-from ..ops import l1, ms_ssim_check, ms_ssim_loss, ms_ssim_weights, ssim_loss
+from ..ops import ffl_check, ffl_loss, l1, ms_ssim_check, ms_ssim_loss, ms_ssim_weights, ssim_loss
 from ..utils.tracing import trace_range
 from .optim import guarded_step, make_adam
 
@@ -40,7 +40,7 @@ class Pix2PixStep:
     def __init__(self, netG, netD, lr=2e-4, beta1=0.5, gan_mode="vanilla", lambda_L1=100.0,
                  reducer_g=None, reducer_d=None, autocast_dtype=None, fuse_d_batch=None,
                  nan_guard=True, packed=None, lambda_ssim=0.0, ssim_window="uniform7",
-                 lambda_msssim=0.0, msssim_scales=5):
+                 lambda_msssim=0.0, msssim_scales=5, lambda_ffl=0.0, ffl_alpha=1.0):
         self.netG, self.netD = netG, netD
         self.criterionGAN = GANLoss(gan_mode=gan_mode)
         self.lambda_L1 = float(lambda_L1)
@@ -49,6 +49,8 @@ class Pix2PixStep:
         # optional multi-scale term lambda_msssim * (1 - MS-SSIM(fake_B, real_B)) over the first
         # msssim_scales of the five weights (renormalised), same window; 0 = not built
         self.lambda_msssim, self.msssim_weights = float(lambda_msssim), ms_ssim_weights(msssim_scales)
+        # optional frequency term lambda_ffl * FFL(fake_B, real_B) (focal frequency loss); 0 = not built
+        self.lambda_ffl, self.ffl_alpha = float(lambda_ffl), float(ffl_alpha)
         self.opt_G = make_adam(netG.parameters(), lr=lr, betas=(beta1, 0.999))
         self.opt_D = make_adam(netD.parameters(), lr=lr, betas=(beta1, 0.999))
         self.reducer_g, self.reducer_d = reducer_g, reducer_d
@@ -124,7 +126,7 @@ class Pix2PixStep:
         from ..models.pix2pix import NLayerDiscriminator, PixelDiscriminator, UnetGenerator
         if self.packed is False or self.fuse_d_batch is False or not self.d_per_sample:
             return False
-        if self.lambda_ssim > 0 or self.lambda_msssim > 0:
+        if self.lambda_ssim > 0 or self.lambda_msssim > 0 or self.lambda_ffl > 0:
             # the packed step keeps fake_B only inside the pair tensor, whose gradient is
             # produced by D's first-conv dgrad: no tensor for a second image loss to read
             return False
@@ -141,6 +143,8 @@ class Pix2PixStep:
         netG, netD = self.netG, self.netD
         if self.lambda_msssim > 0:    # the size rule, before any work of the step
             ms_ssim_check(real_B.shape, self.ssim_window, len(self.msssim_weights), "lambda_msssim")
+        if self.lambda_ffl > 0:
+            ffl_check(real_B.shape, "lambda_ffl")
         native = real_A.is_cuda and _native.get_backend() == "native"
         if native:
             from ..ops import hip
@@ -253,6 +257,9 @@ class Pix2PixStep:
             if self.lambda_msssim > 0:
                 loss_G_MSSSIM = ms_ssim_loss(fake_B, real_B, self.ssim_window, weights=self.msssim_weights)
                 loss_G = loss_G + loss_G_MSSSIM * self.lambda_msssim
+            if self.lambda_ffl > 0:
+                loss_G_FFL = ffl_loss(fake_B, real_B, self.ffl_alpha)
+                loss_G = loss_G + loss_G_FFL * self.lambda_ffl
         with self._phase("G_bwd_opt"):
             self._zero(self.opt_G, self.reducer_g)
             loss_G.backward()
@@ -268,4 +275,6 @@ class Pix2PixStep:
             out["G_SSIM"] = loss_G_SSIM.detach()
         if self.lambda_msssim > 0:
             out["G_MSSSIM"] = loss_G_MSSSIM.detach()
+        if self.lambda_ffl > 0:
+            out["G_FFL"] = loss_G_FFL.detach()
         return out

@@ -81,6 +81,19 @@ class MSSSIMLoss(nn.Module):
         return ops.ms_ssim_loss(pred, target, self.window, self.data_range, self.weights)
 
 
+class FocalFrequencyLoss(nn.Module):
+    """Focal frequency loss of (pred, target) (``ops.ffl_loss``; Jiang et al., ICCV 2021): the
+    squared 2-D spectrum of their difference, each coefficient weighted by ``|F|^alpha`` over
+    its plane's maximum.  H and W: multiples of 32 in [32, 512]."""
+
+    def __init__(self, alpha=1.0):
+        super().__init__()
+        self.alpha = float(alpha)
+
+    def forward(self, pred, target):
+        return ops.ffl_loss(pred, target, self.alpha)
+
+
 class angular_loss(nn.Module):
     """mean(acos(clamp(cos_sim_c(a, b)))) in degrees (networks.py:870-894)."""
 

@@ -183,6 +183,18 @@ def ms_ssim(x, y, window="gauss11", data_range=2.0, weights=MS_SSIM_WEIGHTS):
         return ref.ms_ssim(x, y, window, data_range, weights)
 
 
+ffl_check = ref.ffl_check
+
+
+def ffl_loss(x, y, alpha=1.0):
+    """Focal frequency loss of two [N, C, H, W] images, differentiable in both: the mean of
+    ``w |DFT2_ortho(x - y)|^2`` with the constant ``w = |F|^alpha / max |F|^alpha`` per (n, c)
+    (see ``reference.ffl_loss``).  H and W: multiples of 32 in [32, 512]."""
+    if _native.use_native(x):
+        return _hip().ffl_loss(x, y, alpha)
+    return ref.ffl_loss(x, y, alpha)
+
+
 def augment_pairs(a_u8, b_u8, params, load, crop, dtype=torch.bfloat16, antialias=False):
     """Random resize / crop / flip of cached uint8 [N, H, W, 3] pairs: per row (index, y0, x0,
     flip) of the int32 table ``params``, image ``index`` resized to ``load`` (bicubic, >= the

@@ -1908,6 +1908,37 @@ def ms_ssim(x, y, window="gauss11", data_range=2.0, weights=None):
         return _ms_ssim(x, y, window, data_range, ref.MS_SSIM_WEIGHTS if weights is None else weights)[1]
 
 
+class FFLLossFn(torch.autograd.Function):
+    """Focal frequency loss (csrc/ffl_loss.hip).  Saves only the half spectrum F (fp32,
+    [N, C, 2, H, W / 2 + 1], about 4 bytes per pixel) and the per-plane scales inv [N, C]:
+    neither image.  The gradients take the layout ``empty_like`` would give each image."""
+
+    @staticmethod
+    def forward(ctx, x, y, alpha):
+        if y.dtype != x.dtype:
+            y = y.to(x.dtype)
+        loss, f, inv = P().ffl_loss_fwd(x, y, alpha)
+        like = torch.empty_like(torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device="meta"))
+        ctx.alpha, ctx.strides, ctx.bf16 = alpha, list(like.stride()), x.dtype == torch.bfloat16
+        ctx.save_for_backward(f, inv)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        f, inv = ctx.saved_tensors
+        nx, ny = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx, gy = P().ffl_loss_bwd(f, inv, gout.float().reshape(1), ctx.strides, int(ctx.bf16), ctx.alpha, ny)
+        return (gx if nx else None), (gy if ny else None), None
+
+
+def ffl_loss(x, y, alpha=1.0):
+    from . import reference as ref
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"ffl_loss: fp32 or bf16 images, got {x.dtype}")   # no silent upcast
+    ref.ffl_check(x.shape)
+    return FFLLossFn.apply(x, y, float(alpha))
+
+
 AUGMENT_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
 
 

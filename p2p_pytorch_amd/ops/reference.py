@@ -231,6 +231,52 @@ def ms_ssim_loss(x: torch.Tensor, y: torch.Tensor, window: str = "gauss11", data
     return 1.0 - ms_ssim(x, y, window, data_range, weights).mean()
 
 
+def ffl_check(shape, what: str = "ffl_loss"):
+    """The size rule of the focal frequency loss: H and W each a multiple of 32 in [32, 512]."""
+    if not all(32 <= n <= 512 and n % 32 == 0 for n in shape[-2:]):
+        raise ValueError(f"{what}: H and W must each be a multiple of 32 in [32, 512], "
+                         f"got {shape[-2]}x{shape[-1]}")
+
+
+def _dft_matrix(n: int, dtype, device):
+    """(cos, sin) of 2 pi (k j mod n) / n over sqrt(n), [n, n] each, from float64."""
+    k = torch.arange(n, dtype=torch.int64)
+    t = (2.0 * torch.pi / n) * ((k[:, None] * k[None, :]) % n).double()
+    return ((torch.cos(t) / n ** 0.5).to(dtype=dtype, device=device),
+            (torch.sin(t) / n ** 0.5).to(dtype=dtype, device=device))
+
+
+def ffl_loss(x: torch.Tensor, y: torch.Tensor, alpha: float = 1.0, method: str = "fft") -> torch.Tensor:
+    """Focal frequency loss (Jiang et al., ICCV 2021; the oracle of csrc/ffl_loss.hip).
+
+    With ``F = DFT2_ortho(x - y)`` per (n, c): ``mean_{n,c,u,v} w |F|^2`` where
+    ``w = |F|^alpha / max_{u,v} |F|^alpha`` is a constant (detached; 0 on a plane whose
+    spectrum is zero).  ``method``: ``"fft"`` uses ``torch.fft.fft2``; ``"matrix"`` is the
+    formulation of the kernels, two products against twiddle matrices, row transform first.
+    Keeps the dtype it is given (half types go to fp32).
+    """
+    if x.dtype in (torch.bfloat16, torch.float16):
+        x = x.float()
+    y = y.to(x.dtype)
+    ffl_check(x.shape)
+    d = x - y
+    if method == "fft":
+        f = torch.fft.fft2(d, norm="ortho")
+        p = f.real ** 2 + f.imag ** 2
+    elif method == "matrix":
+        ch, sh = _dft_matrix(d.shape[-2], d.dtype, d.device)
+        cw, sw = _dft_matrix(d.shape[-1], d.dtype, d.device)
+        zr, zi = d @ cw, -(d @ sw)
+        fr, fi = ch @ zr + sh @ zi, ch @ zi - sh @ zr
+        p = fr ** 2 + fi ** 2
+    else:
+        raise ValueError(f"ffl_loss: unknown method {method!r} (fft | matrix)")
+    m = p.detach() ** (0.5 * alpha)
+    mx = m.amax(dim=(2, 3), keepdim=True)
+    w = torch.where(mx > 0, m / mx.clamp_min(torch.finfo(m.dtype).tiny), torch.zeros_like(m))
+    return (w * p).mean()
+
+
 def augment_pairs(a_u8: torch.Tensor, b_u8: torch.Tensor, params: torch.Tensor, load, crop,
                   dtype=torch.bfloat16, antialias: bool = False):
     """Random resize / crop / flip of cached pairs (the oracle of csrc/augment.hip).

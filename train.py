@@ -71,6 +71,11 @@ def build_parser():
     p.add_argument("--lambda_msssim", type=float, default=0.0,
                    help="weight on the multi-scale term 1 - MS-SSIM(fake, real) of the G objective (0 = off); "
                         "its window is --ssim_window")
+    p.add_argument("--lambda_ffl", type=float, default=0.0,
+                   help="weight on the focal frequency loss FFL(fake, real) of the G objective (0 = off); "
+                        "H and W must each be a multiple of 32 in [32, 512]")
+    p.add_argument("--ffl_alpha", type=float, default=1.0,
+                   help="focal frequency loss: exponent of the spectrum weight |F|^alpha / max |F|^alpha")
     p.add_argument("--msssim_scales", type=int, default=5, choices=[1, 2, 3, 4, 5],
                    help="MS-SSIM scales: the first M of the five weights, renormalised; the images need "
                         "min(H, W) >> (M - 1) >= the window size")
@@ -228,7 +233,8 @@ def main(argv=None):
                               autocast_dtype=torch.bfloat16 if (use_cuda and p2p.get_backend() == "torch") else None,
                               nan_guard=not opt.no_nan_guard,
                               lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window,
-                              lambda_msssim=opt.lambda_msssim, msssim_scales=opt.msssim_scales)
+                              lambda_msssim=opt.lambda_msssim, msssim_scales=opt.msssim_scales,
+                              lambda_ffl=opt.lambda_ffl, ffl_alpha=opt.ffl_alpha)
         opt_g, opt_d = trainer.opt_G, trainer.opt_D
     else:
         from p2p_pytorch_amd.engine.compress_gan import CompressGANStep
@@ -239,7 +245,8 @@ def main(argv=None):
                                   reducer_g=reducer_g, reducer_d=reducer_d, reducer_c=reducer_c,
                                   nan_guard=not opt.no_nan_guard,
                                   lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window,
-                                  lambda_msssim=opt.lambda_msssim, msssim_scales=opt.msssim_scales)
+                                  lambda_msssim=opt.lambda_msssim, msssim_scales=opt.msssim_scales,
+                                  lambda_ffl=opt.lambda_ffl, ffl_alpha=opt.ffl_alpha)
         opt_g, opt_d = trainer.opt_g, trainer.opt_d
     # the reference's third optimizer / scheduler pair (train.py:243-246, :441-443): over C
     # when --train_c fixes quirk A1, and stepped + checkpointed like the other two
