@@ -97,6 +97,10 @@ int p2p_ffl_bwd(const float* f, const float* inv, const float* gout, int dtype, 
                 int H, int W, double alpha, const float* twh, const float* tww, float* ysc, void* dx, void* dy,
                 hipStream_t st);
 void p2p_ffl_twiddles(int n, float* out);
+long p2p_gram_ws(int B, int C, int N);
+int p2p_gram_fwd(const void* fx, const void* fy, int B, int C, int N, float* ws, float* d, void* dh, float* loss,
+                 hipStream_t st);
+int p2p_gram_bwd(const void* fx, const void* dh, const float* gout, int B, int C, int N, void* dx, hipStream_t st);
 int p2p_augment_pairs(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
                       int CH, int CW, int dtype, void* out_a, void* out_b, hipStream_t st);
 int p2p_augment_pairs_aa(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
@@ -1663,6 +1667,49 @@ std::vector<Tensor> ffl_loss_bwd(const Tensor& f, const Tensor& inv, const Tenso
   return {dx, dy};
 }
 
+// Gram-matrix style loss (csrc/gram_loss.hip).  Size rule: C a multiple of 64 in [64, 512].
+static void check_gram(const Tensor& f, const char* what) {
+  TORCH_CHECK(f.is_cuda() && f.dim() == 4 && f.scalar_type() == at::kBFloat16 &&
+                  f.is_contiguous(at::MemoryFormat::ChannelsLast),
+              what, ": 4-D bf16 channels_last CUDA features");
+  const int64_t C = f.size(1), N = f.size(2) * f.size(3);
+  TORCH_CHECK_VALUE(C >= 64 && C <= 512 && C % 64 == 0, what, ": C must be a multiple of 64 in [64, 512], got ", C);
+  TORCH_CHECK(f.size(0) >= 1 && N >= 1 && (N + 64) * C * 2 < (int64_t(1) << 31) && f.size(0) < (1 << 20), what,
+              ": B >= 1, H * W >= 1, one image under 2 GiB");
+}
+
+// {loss, D = G(fx) - G(fy) (fp32 [B, C, C]), its bf16 image (the backward's MFMA operand)}
+std::vector<Tensor> gram_loss_fwd(const Tensor& fx, const Tensor& fy) {
+  check_gram(fx, "gram_loss_fwd");
+  check_gram(fy, "gram_loss_fwd");
+  TORCH_CHECK(fx.sizes() == fy.sizes() && fx.device() == fy.device(), "gram_loss_fwd: two feature maps of one shape");
+  const int B = (int)fx.size(0), C = (int)fx.size(1), N = (int)(fx.size(2) * fx.size(3));
+  auto f32 = at::TensorOptions().device(fx.device()).dtype(at::kFloat);
+  Tensor ws = at::empty({p2p_gram_ws(B, C, N)}, f32);   // scratch: dead on return
+  Tensor d = at::empty({B, C, C}, f32), dh = at::empty({B, C, C}, f32.dtype(at::kBFloat16));
+  Tensor loss = at::empty({}, f32);
+  check_rc(p2p_gram_fwd(fx.data_ptr(), fy.data_ptr(), B, C, N, ws.data_ptr<float>(), d.data_ptr<float>(),
+                        dh.data_ptr(), loss.data_ptr<float>(), cur_stream(fx)),
+           "gram_loss_fwd");
+  return {loss, d, dh};
+}
+
+// dL/dfx = gout 4 / (B C^3 N) fx D, in the dtype and strides of fx
+Tensor gram_loss_bwd(const Tensor& fx, const Tensor& dh, const Tensor& gout) {
+  check_gram(fx, "gram_loss_bwd");
+  const int B = (int)fx.size(0), C = (int)fx.size(1), N = (int)(fx.size(2) * fx.size(3));
+  TORCH_CHECK(dh.is_cuda() && dh.scalar_type() == at::kBFloat16 && dh.is_contiguous() && dh.dim() == 3 &&
+                  dh.size(0) == B && dh.size(1) == C && dh.size(2) == C && dh.device() == fx.device(),
+              "gram_loss_bwd: the bf16 image of D of this forward");
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "gram_loss_bwd: gout");
+  Tensor g = gout.contiguous();
+  Tensor dx = at::empty_like(fx);
+  TORCH_CHECK(dx.strides() == fx.strides(), "gram_loss_bwd: gradient strides");
+  check_rc(p2p_gram_bwd(fx.data_ptr(), dh.data_ptr(), g.data_ptr<float>(), B, C, N, dx.data_ptr(), cur_stream(fx)),
+           "gram_loss_bwd");
+  return dx;
+}
+
 // Random resize / crop / flip of cached pairs (csrc/augment.hip).  a, b: the uint8 [N, H, W, 3]
 // cache; params: int32 [B, 4] rows (index, y0, x0, flip).  A CPU table is range-checked here
 // and copied up; a device table is trusted (the kernel clamps each row into range, so a bad
@@ -2291,6 +2338,8 @@ TORCH_LIBRARY(p2p, m) {
         "bool need_x, bool need_y) -> Tensor[]");
   m.def("ffl_loss_fwd(Tensor x, Tensor y, float alpha) -> Tensor[]");
   m.def("ffl_loss_bwd(Tensor f, Tensor inv, Tensor gout, int[] strides, int dtype, float alpha, bool need_y) -> Tensor[]");
+  m.def("gram_loss_fwd(Tensor fx, Tensor fy) -> Tensor[]");
+  m.def("gram_loss_bwd(Tensor fx, Tensor dh, Tensor gout) -> Tensor");
   m.def("augment_pairs(Tensor a, Tensor b, Tensor params, int LH, int LW, int CH, int CW, int dtype, bool antialias=False) -> Tensor[]");
   m.def("quantize(Tensor x, int bits) -> Tensor");
   m.def("quantize_unshuffle(Tensor x, int bits, int r, int cp) -> Tensor[]");
@@ -2373,6 +2422,8 @@ TORCH_LIBRARY_IMPL(p2p, CUDA, m) {
   m.impl("ms_ssim_loss_bwd", ms_ssim_loss_bwd);
   m.impl("ffl_loss_fwd", ffl_loss_fwd);
   m.impl("ffl_loss_bwd", ffl_loss_bwd);
+  m.impl("gram_loss_fwd", gram_loss_fwd);
+  m.impl("gram_loss_bwd", gram_loss_bwd);
   m.impl("augment_pairs", augment_pairs);
   m.impl("quantize", quantize);
   m.impl("quantize_unshuffle", quantize_unshuffle);

@@ -40,7 +40,7 @@ import torch
 
 from .. import _native, ops
 from ..models.losses import GANLoss, calc_tv_Loss
-from ..models.vgg import VGGLoss
+from ..models.vgg import StyleLoss, VGGLoss
 from ..utils.tracing import trace_range
 from .optim import guarded_step, make_adam
 
@@ -66,7 +66,7 @@ class CompressGANStep:
                  train_c=False, c_phase_backward=False, vgg=None, reducer_g=None,
                  reducer_d=None, reducer_c=None, nan_guard=True, lambda_ssim=0.0,
                  ssim_window="uniform7", lambda_msssim=0.0, msssim_scales=5, lambda_ffl=0.0,
-                 ffl_alpha=1.0):
+                 ffl_alpha=1.0, lambda_style=0.0):
         self.net_g, self.net_d, self.net_c = net_g, net_d, net_c
         self.criterionGAN = GANLoss()                      # LSGAN, reference default
         self.criterionVGG = vgg if vgg is not None else VGGLoss()
@@ -82,6 +82,11 @@ class CompressGANStep:
         self.msssim_weights = ops.ms_ssim_weights(msssim_scales)
         # optional frequency term lambda_ffl * FFL(fake_b, real_b) (focal frequency loss); 0 = not built
         self.lambda_ffl, self.ffl_alpha = float(lambda_ffl), float(ffl_alpha)
+        # optional texture term lambda_style * sum_taps gram_loss(phi(fake_b), phi(real_b)) on a second
+        # frozen VGG19 without tap fusion (models.vgg.StyleLoss: one more VGG forward + backward);
+        # 0 = not built
+        self.lambda_style = float(lambda_style)
+        self.criterionStyle = StyleLoss(self.criterionVGG) if self.lambda_style > 0 else None
         self.feat_weights = 4.0 / (n_layers_d + 1)
         self.d_weights = 1.0 / num_d
         self.opt_g = make_adam(net_g.parameters(), lr=lr, betas=(beta1, 0.999))
@@ -203,7 +208,8 @@ class CompressGANStep:
         use_ssim = self.lambda_ssim > 0
         use_msssim = self.lambda_msssim > 0
         use_ffl = self.lambda_ffl > 0
-        fake_d, fake_v, fake_t, *fake_s = ops.fan_out(fake_b, 3 + use_ssim + use_msssim + use_ffl)
+        use_style = self.lambda_style > 0
+        fake_d, fake_v, fake_t, *fake_s = ops.fan_out(fake_b, 3 + use_ssim + use_msssim + use_ffl + use_style)
         pred_fake_g = D(self._d_in(real_a, fake_d))
         # back on before any backward: autograd's AccumulateGrad skips a leaf that no longer
         # requires grad, which would silently drop the D-loss gradients
@@ -231,6 +237,7 @@ class CompressGANStep:
                    and os.environ.get("P2P_VGG_REUSE", "1") != "0" else None)
         vgg_g = self._vgg(fake_v, real_b, fy_real)
         tv = calc_tv_Loss(fake_t)
+        style = self.criterionStyle(fake_s.pop(), real_b) if use_style else None
         ssim = ops.ssim_loss(fake_s[0], real_b, self.ssim_window) if use_ssim else None
         ffl = ops.ffl_loss(fake_s.pop(), real_b, self.ffl_alpha) if use_ffl else None
         msssim = (ops.ms_ssim_loss(fake_s[-1], real_b, self.ssim_window, weights=self.msssim_weights)
@@ -244,6 +251,8 @@ class CompressGANStep:
                 terms, weights = terms + [msssim], weights + [self.lambda_msssim]
             if use_ffl:
                 terms, weights = terms + [ffl], weights + [self.lambda_ffl]
+            if use_style:
+                terms, weights = terms + [style], weights + [self.lambda_style]
             loss_g = ops.lincomb_n(terms, weights)
             with torch.no_grad():
                 content = ops.lincomb_n([vgg_g.detach()], [self.lambda_vgg])
@@ -256,6 +265,8 @@ class CompressGANStep:
                 loss_g = loss_g + msssim * self.lambda_msssim
             if use_ffl:
                 loss_g = loss_g + ffl * self.lambda_ffl
+            if use_style:
+                loss_g = loss_g + style * self.lambda_style
         # ---- updates: G first (its backward also reaches D; those grads are dropped)
         with self._phase("G_bwd_opt"):
             self._zero(self.opt_g, self.reducer_g)
@@ -306,4 +317,6 @@ class CompressGANStep:
             out["MSSSIM"] = msssim.detach()
         if use_ffl:
             out["FFL"] = ffl.detach()
+        if use_style:
+            out["Style"] = style.detach()
         return out

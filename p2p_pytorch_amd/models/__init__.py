@@ -7,6 +7,6 @@ from .layers import BatchNorm2d, Conv2d, ConvTranspose2d, InstanceNorm2d
 from .losses import GANLoss, angular_loss, calc_tv_Loss, sobelLayer
 from .pix2pix import NLayerDiscriminator, PixelDiscriminator, UnetGenerator
 from .pix2pix import NLayerDiscriminator as PatchGANDiscriminator
-from .vgg import VGGLoss, Vgg19
+from .vgg import StyleLoss, VGGLoss, Vgg19
 
 __all__ = [n for n in dir() if not n.startswith("_")]

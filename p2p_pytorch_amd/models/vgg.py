@@ -158,3 +158,30 @@ class VGGLoss(nn.Module):
                 terms.append(ops.l1(a, b.detach()))
         # the weighted sum in one launch each way on the native path (ops.lincomb_n)
         return ops.lincomb_n(terms, self.weights[:len(terms)])
+
+
+class StyleLoss(nn.Module):
+    """sum_i gram_loss(phi_i(x), phi_i(y)) over the five taps, each with weight 1 (Gatys et al.,
+    Johnson et al.: the distance between Gram matrices of VGG19 features; ``ops.gram_loss``).
+
+    Owns a SECOND frozen ``Vgg19`` whose weights are loaded from the ``VGGLoss`` it is given.
+    The perceptual loss's network runs with tap fusion, where a tap's one gradient is parked
+    for the tap's consumer conv; a second gradient on the same tap has no place there.  This
+    network keeps tap fusion off, so its taps are ordinary outputs and autograd sums the two
+    gradients of each.  The price is one more VGG19 forward and backward on ``x`` (and a
+    gradient-free forward on ``y``) whenever the term is on."""
+
+    def __init__(self, vgg_loss: VGGLoss):
+        super().__init__()
+        self.vgg = Vgg19()
+        self.vgg.load_state_dict(vgg_loss.vgg.state_dict())
+        self.vgg.pretrained = vgg_loss.vgg.pretrained
+        self.vgg.to(next(vgg_loss.vgg.parameters()).device)
+
+    def forward(self, x, y):
+        with torch.no_grad():
+            fy = self.vgg(y)
+        for f in fy:
+            ops.gram_check(f.shape, "StyleLoss")
+        terms = [ops.gram_loss(a, b) for a, b in zip(self.vgg(x), fy)]
+        return ops.lincomb_n(terms, [1.0] * len(terms))

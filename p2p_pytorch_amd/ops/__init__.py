@@ -195,6 +195,19 @@ def ffl_loss(x, y, alpha=1.0):
     return ref.ffl_loss(x, y, alpha)
 
 
+gram_check = ref.gram_check
+
+
+def gram_loss(fx, fy):
+    """Gram-matrix style loss of two [B, C, H, W] feature maps, differentiable in ``fx`` (``fy``
+    is a constant): ``mean (G(fx) - G(fy))^2`` with ``G(F)_b = F_b F_b^T / (C H W)`` (see
+    ``reference.gram_loss``).  C: a multiple of 64 in [64, 512].  Native path: bf16
+    channels_last features only (``TypeError`` otherwise), fp32 value."""
+    if _native.use_native(fx):
+        return _hip().gram_loss(fx, fy)
+    return ref.gram_loss(fx, fy)
+
+
 def augment_pairs(a_u8, b_u8, params, load, crop, dtype=torch.bfloat16, antialias=False):
     """Random resize / crop / flip of cached uint8 [N, H, W, 3] pairs: per row (index, y0, x0,
     flip) of the int32 table ``params``, image ``index`` resized to ``load`` (bicubic, >= the

@@ -1939,6 +1939,36 @@ def ffl_loss(x, y, alpha=1.0):
     return FFLLossFn.apply(x, y, float(alpha))
 
 
+class GramLossFn(torch.autograd.Function):
+    """Gram-matrix style loss (csrc/gram_loss.hip).  Saves fx and the bf16 image of
+    D = G(fx) - G(fy) ([B, C, C]); the gradient has the dtype and strides of fx."""
+
+    @staticmethod
+    def forward(ctx, fx, fy):
+        loss, _, dh = P().gram_loss_fwd(fx, fy)
+        ctx.save_for_backward(fx, dh)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        fx, dh = ctx.saved_tensors
+        return P().gram_loss_bwd(fx, dh, gout.float().reshape(1)), None
+
+
+def gram_loss(fx, fy):
+    from . import reference as ref
+    if fy.requires_grad:
+        raise ValueError("gram_loss: fy is a constant target; detach it")
+    for name, f in (("fx", fx), ("fy", fy)):   # no silent upcast, no silent re-layout
+        if f.dtype != torch.bfloat16 or f.dim() != 4 or not f.is_contiguous(memory_format=torch.channels_last):
+            raise TypeError(f"gram_loss: {name} must be bf16 channels_last [B, C, H, W] features, got {f.dtype} "
+                            f"with strides {tuple(f.stride())}")
+    ref.gram_check(fx.shape)
+    if fx.shape != fy.shape:
+        raise ValueError(f"gram_loss: shapes differ, {tuple(fx.shape)} and {tuple(fy.shape)}")
+    return GramLossFn.apply(fx, fy)
+
+
 AUGMENT_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
 
 

@@ -277,6 +277,34 @@ def ffl_loss(x: torch.Tensor, y: torch.Tensor, alpha: float = 1.0, method: str =
     return (w * p).mean()
 
 
+def gram_check(shape, what: str = "gram_loss"):
+    """The size rule of the Gram-matrix style loss: [B, C, H, W] features with C a multiple of
+    64 in [64, 512] (every VGG19 tap) and at least one pixel."""
+    if len(shape) != 4 or not (64 <= shape[1] <= 512 and shape[1] % 64 == 0):
+        raise ValueError(f"{what}: C must be a multiple of 64 in [64, 512], got shape {tuple(shape)}")
+    if shape[0] < 1 or shape[2] * shape[3] < 1:
+        raise ValueError(f"{what}: B >= 1 and H * W >= 1, got shape {tuple(shape)}")
+
+
+def gram_loss(fx: torch.Tensor, fy: torch.Tensor) -> torch.Tensor:
+    """Gram-matrix style loss of two [B, C, H, W] feature maps (Gatys et al.; the oracle of
+    csrc/gram_loss.hip): ``mean_{b,i,j} (G(fx) - G(fy))^2`` with ``G(F)_b = F_b F_b^T / (C N)``,
+    ``F_b`` image b as C x N, N = H W.  ``fy`` is a constant.  Keeps the dtype it is given (half
+    types go to fp32)."""
+    if fy.requires_grad:
+        raise ValueError("gram_loss: fy is a constant target; detach it")
+    if fx.dtype in (torch.bfloat16, torch.float16):
+        fx = fx.float()
+    fy = fy.to(fx.dtype)
+    gram_check(fx.shape)
+    if fx.shape != fy.shape:
+        raise ValueError(f"gram_loss: shapes differ, {tuple(fx.shape)} and {tuple(fy.shape)}")
+    b, c, h, w = fx.shape
+    x, y = fx.reshape(b, c, h * w), fy.reshape(b, c, h * w)
+    d = (x @ x.transpose(1, 2) - y @ y.transpose(1, 2)) / (c * h * w)
+    return (d * d).mean()
+
+
 def augment_pairs(a_u8: torch.Tensor, b_u8: torch.Tensor, params: torch.Tensor, load, crop,
                   dtype=torch.bfloat16, antialias: bool = False):
     """Random resize / crop / flip of cached pairs (the oracle of csrc/augment.hip).

@@ -76,6 +76,9 @@ def build_parser():
                         "H and W must each be a multiple of 32 in [32, 512]")
     p.add_argument("--ffl_alpha", type=float, default=1.0,
                    help="focal frequency loss: exponent of the spectrum weight |F|^alpha / max |F|^alpha")
+    p.add_argument("--lambda_style", type=float, default=0.0,
+                   help="reference family: weight on the Gram-matrix style loss of the five VGG19 taps of "
+                        "(fake, real) in the G objective (0 = off); costs one more VGG19 forward and backward")
     p.add_argument("--msssim_scales", type=int, default=5, choices=[1, 2, 3, 4, 5],
                    help="MS-SSIM scales: the first M of the five weights, renormalised; the images need "
                         "min(H, W) >> (M - 1) >= the window size")
@@ -135,7 +138,11 @@ def build_parser():
 
 
 def main(argv=None):
-    opt = build_parser().parse_args(argv)
+    parser = build_parser()
+    opt = parser.parse_args(argv)
+    if opt.lambda_style > 0 and opt.netG.startswith("unet"):
+        parser.error("--lambda_style needs the reference family's VGG19 (--netG expand); "
+                     f"the pix2pix family (--netG {opt.netG}) has none")
     import p2p_pytorch_amd as p2p
     from p2p_pytorch_amd.data import (DevicePairCache, SyntheticPairs, get_test_set,
                                       get_training_set)
@@ -246,7 +253,8 @@ def main(argv=None):
                                   nan_guard=not opt.no_nan_guard,
                                   lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window,
                                   lambda_msssim=opt.lambda_msssim, msssim_scales=opt.msssim_scales,
-                                  lambda_ffl=opt.lambda_ffl, ffl_alpha=opt.ffl_alpha)
+                                  lambda_ffl=opt.lambda_ffl, ffl_alpha=opt.ffl_alpha,
+                                  lambda_style=opt.lambda_style)
         opt_g, opt_d = trainer.opt_g, trainer.opt_d
     # the reference's third optimizer / scheduler pair (train.py:243-246, :441-443): over C
     # when --train_c fixes quirk A1, and stepped + checkpointed like the other two
