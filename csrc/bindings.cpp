@@ -14,6 +14,7 @@
 #include <torch/library.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -1446,20 +1447,41 @@ Tensor tv_fwd(const Tensor& x) {
   return out;
 }
 
+// What the image losses (SSIM, MS-SSIM, focal frequency, Gram) share.  Two [N, C, H, W] images
+// of one shape and dtype (fp32 or bf16), any strides:
+static void check_image_pair(const Tensor& x, const Tensor& y, const char* what) {
+  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.dim() == 4 && x.sizes() == y.sizes(), what,
+              ": two 4-D CUDA tensors of one shape");
+  TORCH_CHECK(x.scalar_type() == y.scalar_type() &&
+                  (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
+              what, ": fp32 or bf16 inputs of one dtype");
+}
+
+static int dtype_code(const Tensor& t) { return t.scalar_type() == at::kBFloat16 ? 1 : 0; }   // 0 = fp32
+
+// the element strides (n, c, h, w) of up to three images, one after the other
+static std::array<long, 12> image_strides(std::initializer_list<const Tensor*> images) {
+  std::array<long, 12> s{};
+  long* p = s.data();
+  for (const Tensor* t : images)
+    for (int i = 0; i < 4; ++i) *p++ = (long)t->stride(i);
+  return s;
+}
+
+// dL/dloss: one fp32 value on the device
+static Tensor loss_gout(const Tensor& gout, const char* what) {
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, what, ": gout");
+  return gout.contiguous();
+}
+
 // per-image (PSNR, SSIM) of two [N, C, H, W] image batches (any strides, fp32 or bf16):
 // returns float64 [N, 2]
 Tensor image_metrics(const Tensor& a, const Tensor& b, bool shift, double data_range) {
-  TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.dim() == 4 && a.sizes() == b.sizes(),
-              "image_metrics: two 4-D CUDA tensors of one shape");
-  TORCH_CHECK(a.scalar_type() == b.scalar_type() &&
-                  (a.scalar_type() == at::kFloat || a.scalar_type() == at::kBFloat16),
-              "image_metrics: fp32 or bf16 inputs of one dtype");
+  check_image_pair(a, b, "image_metrics");
   const int N = (int)a.size(0), C = (int)a.size(1), H = (int)a.size(2), W = (int)a.size(3);
   TORCH_CHECK(H >= 7 && W >= 7, "image_metrics: images of at least 7x7 (SSIM window)");
-  const long st[8] = {(long)a.stride(0), (long)a.stride(1), (long)a.stride(2), (long)a.stride(3),
-                      (long)b.stride(0), (long)b.stride(1), (long)b.stride(2), (long)b.stride(3)};
   Tensor ws = at::empty({N, p2p_metrics_ws(C, H, W), 2}, a.options().dtype(at::kDouble));
-  check_rc(p2p_image_metrics(a.data_ptr(), b.data_ptr(), a.scalar_type() == at::kBFloat16 ? 1 : 0, st, N, C, H,
+  check_rc(p2p_image_metrics(a.data_ptr(), b.data_ptr(), dtype_code(a), image_strides({&a, &b}).data(), N, C, H,
                              W, shift ? 1 : 0, data_range, ws.data_ptr<double>(), cur_stream(a)),
            "image_metrics");
   Tensor sums = ws.sum(1);  // fixed-order reduction of the per-tile partials
@@ -1469,14 +1491,26 @@ Tensor image_metrics(const Tensor& a, const Tensor& b, bool shift, double data_r
   return at::stack({psnr, ssim}, 1);
 }
 
-// SSIM loss (csrc/ssim_loss.hip): two [N, C, H, W] images of one shape and dtype (fp32 or
-// bf16), any strides.  window: 0 = uniform7, 1 = gauss11.
+// {dL/dx, dL/dy} (undefined where not needed), each laid out like its image, of a loss that is
+// symmetric in its two images: dL/dy is dL/dx with the images swapped.  launch(a, b, d,
+// strides of (a, b, d), swap) writes d = dL/da and returns the kernel's code.
+template <typename F>
+static std::vector<Tensor> image_grad_pair(const Tensor& x, const Tensor& y, bool need_x, bool need_y,
+                                           const char* what, F&& launch) {
+  auto run = [&](const Tensor& a, const Tensor& b, int swap) {
+    Tensor d = at::empty_like(a);
+    check_rc(launch(a, b, d, image_strides({&a, &b, &d}).data(), swap), what);
+    return d;
+  };
+  Tensor gx, gy;
+  if (need_x) gx = run(x, y, 0);
+  if (need_y) gy = run(y, x, 1);
+  return {gx, gy};
+}
+
+// SSIM loss (csrc/ssim_loss.hip).  window: 0 = uniform7, 1 = gauss11.
 static void check_ssim(const Tensor& x, const Tensor& y, int64_t window, const char* what) {
-  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.dim() == 4 && x.sizes() == y.sizes(), what,
-              ": two 4-D CUDA tensors of one shape");
-  TORCH_CHECK(x.scalar_type() == y.scalar_type() &&
-                  (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
-              what, ": fp32 or bf16 inputs of one dtype");
+  check_image_pair(x, y, what);
   TORCH_CHECK(window == 0 || window == 1, what, ": window 0 (uniform7) or 1 (gauss11)");
   const int64_t k = window == 1 ? 11 : 7;
   TORCH_CHECK(x.size(2) >= k && x.size(3) >= k, what, ": images of at least ", k, "x", k, " (the window)");
@@ -1485,39 +1519,23 @@ static void check_ssim(const Tensor& x, const Tensor& y, int64_t window, const c
 Tensor ssim_loss_fwd(const Tensor& x, const Tensor& y, int64_t window, double data_range) {
   check_ssim(x, y, window, "ssim_loss_fwd");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
-  const long st[8] = {(long)x.stride(0), (long)x.stride(1), (long)x.stride(2), (long)x.stride(3),
-                      (long)y.stride(0), (long)y.stride(1), (long)y.stride(2), (long)y.stride(3)};
   Tensor ws = at::empty({p2p_ssim_loss_ws(N, C, H, W, (int)window)}, x.options().dtype(at::kFloat));
   Tensor out = at::empty({}, x.options().dtype(at::kFloat));
-  check_rc(p2p_ssim_loss_fwd(x.data_ptr(), y.data_ptr(), x.scalar_type() == at::kBFloat16 ? 1 : 0, st, N, C, H,
-                             W, (int)window, data_range, ws.data_ptr<float>(), out.data_ptr<float>(),
-                             cur_stream(x)),
+  check_rc(p2p_ssim_loss_fwd(x.data_ptr(), y.data_ptr(), dtype_code(x), image_strides({&x, &y}).data(), N, C, H, W,
+                             (int)window, data_range, ws.data_ptr<float>(), out.data_ptr<float>(), cur_stream(x)),
            "ssim_loss_fwd");
   return out;
 }
 
-// {dL/dx, dL/dy} (undefined where not needed), each laid out like its image
 std::vector<Tensor> ssim_loss_bwd(const Tensor& x, const Tensor& y, int64_t window, double data_range,
                                   const Tensor& gout, bool need_x, bool need_y) {
   check_ssim(x, y, window, "ssim_loss_bwd");
-  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "ssim_loss_bwd: gout");
-  Tensor g = gout.contiguous();
+  Tensor g = loss_gout(gout, "ssim_loss_bwd");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
-  const int dt = x.scalar_type() == at::kBFloat16 ? 1 : 0;
-  auto run = [&](const Tensor& a, const Tensor& b) {   // dL/da: S is symmetric in its two images
-    Tensor d = at::empty_like(a);
-    const long st[12] = {(long)a.stride(0), (long)a.stride(1), (long)a.stride(2), (long)a.stride(3),
-                         (long)b.stride(0), (long)b.stride(1), (long)b.stride(2), (long)b.stride(3),
-                         (long)d.stride(0), (long)d.stride(1), (long)d.stride(2), (long)d.stride(3)};
-    check_rc(p2p_ssim_loss_bwd(a.data_ptr(), b.data_ptr(), dt, st, N, C, H, W, (int)window, data_range,
-                               g.data_ptr<float>(), d.data_ptr(), cur_stream(a)),
-             "ssim_loss_bwd");
-    return d;
-  };
-  Tensor gx, gy;
-  if (need_x) gx = run(x, y);
-  if (need_y) gy = run(y, x);
-  return {gx, gy};
+  return image_grad_pair(x, y, need_x, need_y, "ssim_loss_bwd", [&](auto& a, auto& b, auto& d, auto* st, int) {
+    return p2p_ssim_loss_bwd(a.data_ptr(), b.data_ptr(), dtype_code(a), st, N, C, H, W, (int)window, data_range,
+                             g.data_ptr<float>(), d.data_ptr(), cur_stream(a));
+  });
 }
 
 // Multi-scale SSIM loss (csrc/ms_ssim_loss.hip): the checks of check_ssim plus the size rule
@@ -1536,27 +1554,24 @@ std::vector<Tensor> ms_ssim_loss_fwd(const Tensor& x, const Tensor& y, int64_t w
   const int M = (int)weights.size();
   check_ms_ssim(x, y, window, M, "ms_ssim_loss_fwd");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
-  const long st[8] = {(long)x.stride(0), (long)x.stride(1), (long)x.stride(2), (long)x.stride(3),
-                      (long)y.stride(0), (long)y.stride(1), (long)y.stride(2), (long)y.stride(3)};
   auto f32 = x.options().dtype(at::kFloat);
   Tensor pyr = at::empty({p2p_ms_ssim_pyr(N, C, H, W, M)}, f32);
   Tensor ws = at::empty({p2p_ms_ssim_ws(N, C, H, W, M)}, f32);
   Tensor ms = at::empty({N, C}, f32), coef = at::empty({M, N, C}, f32), loss = at::empty({}, f32);
-  check_rc(p2p_ms_ssim_fwd(x.data_ptr(), y.data_ptr(), x.scalar_type() == at::kBFloat16 ? 1 : 0, st, N, C, H, W,
+  check_rc(p2p_ms_ssim_fwd(x.data_ptr(), y.data_ptr(), dtype_code(x), image_strides({&x, &y}).data(), N, C, H, W,
                            (int)window, data_range, weights.data(), M, pyr.data_ptr<float>(), ws.data_ptr<float>(),
                            ms.data_ptr<float>(), coef.data_ptr<float>(), loss.data_ptr<float>(), cur_stream(x)),
            "ms_ssim_loss_fwd");
   return {loss, ms, pyr, coef};
 }
 
-// {dL/dx, dL/dy} (undefined where not needed), each laid out like its image
 std::vector<Tensor> ms_ssim_loss_bwd(const Tensor& x, const Tensor& y, const Tensor& pyr, const Tensor& coef,
                                      int64_t window, double data_range, const Tensor& gout, bool need_x,
                                      bool need_y) {
   TORCH_CHECK(coef.dim() == 3, "ms_ssim_loss_bwd: coef [M, N, C]");
   const int M = (int)coef.size(0);
   check_ms_ssim(x, y, window, M, "ms_ssim_loss_bwd");
-  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "ms_ssim_loss_bwd: gout");
+  Tensor g = loss_gout(gout, "ms_ssim_loss_bwd");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
   TORCH_CHECK(pyr.is_cuda() && pyr.scalar_type() == at::kFloat && pyr.is_contiguous() &&
                   pyr.numel() == p2p_ms_ssim_pyr(N, C, H, W, M),
@@ -1564,25 +1579,13 @@ std::vector<Tensor> ms_ssim_loss_bwd(const Tensor& x, const Tensor& y, const Ten
   TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.size(1) == N &&
                   coef.size(2) == C,
               "ms_ssim_loss_bwd: the coefficients of this forward");
-  Tensor g = gout.contiguous();
-  const int dt = x.scalar_type() == at::kBFloat16 ? 1 : 0;
   // gradients of the coarser scales (fp32, half the pyramid): dead after the call
   Tensor gtmp = at::empty({pyr.numel() / 2}, pyr.options());
-  auto run = [&](const Tensor& a, const Tensor& b, int swap) {
-    Tensor d = at::empty_like(a);
-    const long st[12] = {(long)a.stride(0), (long)a.stride(1), (long)a.stride(2), (long)a.stride(3),
-                         (long)b.stride(0), (long)b.stride(1), (long)b.stride(2), (long)b.stride(3),
-                         (long)d.stride(0), (long)d.stride(1), (long)d.stride(2), (long)d.stride(3)};
-    check_rc(p2p_ms_ssim_bwd(a.data_ptr(), b.data_ptr(), dt, st, N, C, H, W, (int)window, data_range, M,
-                             pyr.data_ptr<float>(), swap, coef.data_ptr<float>(), g.data_ptr<float>(),
-                             gtmp.data_ptr<float>(), d.data_ptr(), cur_stream(a)),
-             "ms_ssim_loss_bwd");
-    return d;
-  };
-  Tensor gx, gy;
-  if (need_x) gx = run(x, y, 0);
-  if (need_y) gy = run(y, x, 1);
-  return {gx, gy};
+  return image_grad_pair(x, y, need_x, need_y, "ms_ssim_loss_bwd", [&](auto& a, auto& b, auto& d, auto* st, int swap) {
+    return p2p_ms_ssim_bwd(a.data_ptr(), b.data_ptr(), dtype_code(a), st, N, C, H, W, (int)window, data_range, M,
+                           pyr.data_ptr<float>(), swap, coef.data_ptr<float>(), g.data_ptr<float>(),
+                           gtmp.data_ptr<float>(), d.data_ptr(), cur_stream(a));
+  });
 }
 
 // Focal frequency loss (csrc/ffl_loss.hip).  Size rule: H and W each a multiple of 32 in
@@ -1612,24 +1615,18 @@ static Tensor ffl_twiddles(int64_t n, const at::Device& dev) {
 
 // {loss, F (the half spectrum, fp32 [N, C, 2, H, W / 2 + 1]), inv [N, C]}: all the backward needs
 std::vector<Tensor> ffl_loss_fwd(const Tensor& x, const Tensor& y, double alpha) {
-  TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.dim() == 4 && x.sizes() == y.sizes(),
-              "ffl_loss_fwd: two 4-D CUDA tensors of one shape");
-  TORCH_CHECK(x.scalar_type() == y.scalar_type() &&
-                  (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
-              "ffl_loss_fwd: fp32 or bf16 inputs of one dtype");
+  check_image_pair(x, y, "ffl_loss_fwd");
   TORCH_CHECK(alpha >= 0.0, "ffl_loss_fwd: alpha >= 0");
   check_ffl_size(x.size(2), x.size(3), "ffl_loss_fwd");
   TORCH_CHECK(x.size(0) >= 1 && x.size(1) >= 1 && x.size(0) * x.size(1) < (1 << 26), "ffl_loss_fwd: N * C");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
-  const long st[8] = {(long)x.stride(0), (long)x.stride(1), (long)x.stride(2), (long)x.stride(3),
-                      (long)y.stride(0), (long)y.stride(1), (long)y.stride(2), (long)y.stride(3)};
   auto f32 = x.options().dtype(at::kFloat);
   Tensor twh = ffl_twiddles(H, x.device()), tww = ffl_twiddles(W, x.device());
   Tensor z = at::empty({p2p_ffl_spec(N, C, H, W)}, f32);   // scratch: dead on return
   Tensor f = at::empty({N, C, 2, H, W / 2 + 1}, f32);
   Tensor ws = at::empty({p2p_ffl_ws(N, C, H, W)}, f32);
   Tensor inv = at::empty({N, C}, f32), loss = at::empty({}, f32);
-  check_rc(p2p_ffl_fwd(x.data_ptr(), y.data_ptr(), x.scalar_type() == at::kBFloat16 ? 1 : 0, st, N, C, H, W, alpha,
+  check_rc(p2p_ffl_fwd(x.data_ptr(), y.data_ptr(), dtype_code(x), image_strides({&x, &y}).data(), N, C, H, W, alpha,
                        twh.data_ptr<float>(), tww.data_ptr<float>(), z.data_ptr<float>(), f.data_ptr<float>(),
                        ws.data_ptr<float>(), inv.data_ptr<float>(), loss.data_ptr<float>(), cur_stream(x)),
            "ffl_loss_fwd");
@@ -1648,9 +1645,8 @@ std::vector<Tensor> ffl_loss_bwd(const Tensor& f, const Tensor& inv, const Tenso
   TORCH_CHECK(inv.is_cuda() && inv.scalar_type() == at::kFloat && inv.is_contiguous() && inv.dim() == 2 &&
                   inv.size(0) == N && inv.size(1) == C,
               "ffl_loss_bwd: the per-plane scales of this forward");
-  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "ffl_loss_bwd: gout");
+  Tensor g = loss_gout(gout, "ffl_loss_bwd");
   TORCH_CHECK(strides.size() == 4 && (dtype == 0 || dtype == 1), "ffl_loss_bwd: 4 strides, dtype 0 | 1");
-  Tensor g = gout.contiguous();
   auto opt = f.options().dtype(dtype == 1 ? at::kBFloat16 : at::kFloat);
   Tensor dx = at::empty_strided({N, C, H, W}, strides, opt);
   TORCH_CHECK(dx.is_non_overlapping_and_dense(), "ffl_loss_bwd: dense gradient strides");
@@ -1701,8 +1697,7 @@ Tensor gram_loss_bwd(const Tensor& fx, const Tensor& dh, const Tensor& gout) {
   TORCH_CHECK(dh.is_cuda() && dh.scalar_type() == at::kBFloat16 && dh.is_contiguous() && dh.dim() == 3 &&
                   dh.size(0) == B && dh.size(1) == C && dh.size(2) == C && dh.device() == fx.device(),
               "gram_loss_bwd: the bf16 image of D of this forward");
-  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kFloat && gout.numel() == 1, "gram_loss_bwd: gout");
-  Tensor g = gout.contiguous();
+  Tensor g = loss_gout(gout, "gram_loss_bwd");
   Tensor dx = at::empty_like(fx);
   TORCH_CHECK(dx.strides() == fx.strides(), "gram_loss_bwd: gradient strides");
   check_rc(p2p_gram_bwd(fx.data_ptr(), dh.data_ptr(), g.data_ptr<float>(), B, C, N, dx.data_ptr(), cur_stream(fx)),

@@ -916,6 +916,13 @@ int p2p_sum_partials(const float* ws, int nb, float scale, float* out, hipStream
   return (int)hipGetLastError();
 }
 
+// out[0] = scale * sum(v[0..n)) in a fixed order; v + n: 256 floats of workspace (used past
+// 4096 values)
+int p2p_sum_fixed(const float* v, long n, float scale, float* out, hipStream_t st) {
+  if (n <= 4096) return p2p_sum_partials(v, (int)n, scale, out, st);
+  return p2p_sum_long(v, n, scale, const_cast<float*>(v) + n, out, st);
+}
+
 int p2p_loss_bwd(const void* a, const void* b, int is_f32, long n, int kind, float t, float scale,
                  const float* gout, void* ga, void* gb, hipStream_t st) {
   using namespace p2p;

@@ -56,17 +56,7 @@
 // floats (68 KB at 512, 35 KB at 256).  The transposed strips have the odd stride 33 so the
 // staging writes (lanes along w) and the fragment reads (lanes along the row) are both
 // conflict-free within each half wave; the column strips are read as 64 consecutive words.
-#include "common.h"
-
-extern "C" int p2p_sum_partials(const float* ws, int nb, float scale, float* out, hipStream_t st);
-extern "C" int p2p_sum_long(const float* ws, long n, float scale, float* part, float* out, hipStream_t st);
-
-// no packed fp32 arithmetic in these kernels: see ssim_loss.hip
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FFL_SCALAR_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define FFL_SCALAR_F32
-#endif
+#include "common.h"   // P2P_SCALAR_F32: no packed fp32 arithmetic in these kernels
 
 namespace p2p {
 
@@ -113,7 +103,7 @@ struct FflArgs {
 
 // p^(alpha / 2) for p = |F|^2 >= 0: the focal weight up to the per-plane scale.  alpha 0, 1
 // and 2 avoid powf (exact, sqrt, exact).
-__device__ __forceinline__ FFL_SCALAR_F32 float ffl_weight(float p, float alpha) {
+__device__ __forceinline__ P2P_SCALAR_F32 float ffl_weight(float p, float alpha) {
   if (alpha == 0.f) return 1.f;
   if (alpha == 1.f) return sqrtf(p);
   if (alpha == 2.f) return p;
@@ -128,7 +118,7 @@ __device__ __forceinline__ int ffl_acc_row(int r, int lane) { return (r >> 2) * 
 // Passes 1 and 5.  One workgroup = rows r0 .. r0 + 31 of one plane; wave t = output columns
 // 32 t ...  A (the strip, k-major in LDS) x B (twiddle rows from global memory).
 template <typename T, bool INV>
-__global__ void FFL_SCALAR_F32 __launch_bounds__(1024) ffl_row_kernel(FflArgs m) {
+__global__ void P2P_SCALAR_F32 __launch_bounds__(1024) ffl_row_kernel(FflArgs m) {
   extern __shared__ float ffl_lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int strips = m.H / FFL_T;
@@ -206,7 +196,7 @@ __global__ void FFL_SCALAR_F32 __launch_bounds__(1024) ffl_row_kernel(FflArgs m)
 // = output rows 32 t ...  A (twiddle, read as rows of the symmetric matrix) x B (the strip).
 // out = (C -+ iS) in:  re = C re +- S im,  im = C im -+ S re  (upper sign: forward).
 template <bool INV>
-__global__ void FFL_SCALAR_F32 __launch_bounds__(1024) ffl_col_kernel(FflArgs m) {
+__global__ void P2P_SCALAR_F32 __launch_bounds__(1024) ffl_col_kernel(FflArgs m) {
   extern __shared__ float ffl_lds[];
   __shared__ float red[2][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -354,8 +344,7 @@ extern "C" int p2p_ffl_fwd(const void* x, const void* y, int dtype, const long* 
   int rc = (int)hipGetLastError();
   if (rc) return rc;
   const float scale = (float)(1.0 / ((double)planes * H * W));
-  if (planes <= 4096) return p2p_sum_partials(term, (int)planes, scale, loss, st);
-  return p2p_sum_long(term, planes, scale, term + planes, loss, st);
+  return p2p_sum_fixed(term, planes, scale, loss, st);
 }
 
 // strides[8] = (n, c, h, w) of dx, then of dy (dy may be null: only dx is written).

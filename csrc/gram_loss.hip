@@ -49,9 +49,6 @@
 //                  tile would buy nothing.
 #include "common.h"
 
-extern "C" int p2p_sum_partials(const float* ws, int nb, float scale, float* out, hipStream_t st);
-extern "C" int p2p_sum_long(const float* ws, long n, float scale, float* part, float* out, hipStream_t st);
-
 namespace p2p {
 namespace {
 
@@ -565,8 +562,7 @@ extern "C" int p2p_gram_fwd(const void* fx, const void* fy, int B, int C, int N,
   int rc = (int)hipGetLastError();
   if (rc) return rc;
   const float scale = (float)(1.0 / ((double)B * C * C));
-  if (tiles <= 4096) return p2p_sum_partials(part, (int)tiles, scale, loss, st);
-  return p2p_sum_long(part, tiles, scale, part + tiles, loss, st);
+  return p2p_sum_fixed(part, tiles, scale, loss, st);
 }
 
 // dx[B][N][C] = gout 4 / (B C^3 N) fx D, D from dh (the bf16 image of the forward)

@@ -39,7 +39,7 @@ import os
 import torch
 
 from .. import _native, ops
-from ..models.losses import GANLoss, calc_tv_Loss
+from ..models.losses import GANLoss, ImageTerms, calc_tv_Loss
 from ..models.vgg import StyleLoss, VGGLoss
 from ..utils.tracing import trace_range
 from .optim import guarded_step, make_adam
@@ -74,19 +74,17 @@ class CompressGANStep:
         self.criterionVGG.to(dev)
         self.bits = bits
         self.lambda_feat, self.lambda_vgg, self.lambda_tv = lambda_feat, lambda_vgg, lambda_tv
-        # optional structural term lambda_ssim * (1 - SSIM(fake_b, real_b)); 0 = not built
+        # optional terms lambda * term(fake_b, real_b), 0 = not built: 1 - SSIM, 1 - MS-SSIM over the
+        # first msssim_scales of the five weights (renormalised, same window), focal frequency loss,
+        # and the texture term sum_taps gram_loss(phi(fake_b), phi(real_b)) on a second frozen VGG19
+        # without tap fusion (models.vgg.StyleLoss: one more VGG forward + backward)
         self.lambda_ssim, self.ssim_window = float(lambda_ssim), ssim_window
-        # optional multi-scale term lambda_msssim * (1 - MS-SSIM(fake_b, real_b)) over the first
-        # msssim_scales of the five weights (renormalised), same window; 0 = not built
-        self.lambda_msssim = float(lambda_msssim)
-        self.msssim_weights = ops.ms_ssim_weights(msssim_scales)
-        # optional frequency term lambda_ffl * FFL(fake_b, real_b) (focal frequency loss); 0 = not built
+        self.lambda_msssim, self.msssim_weights = float(lambda_msssim), ops.ms_ssim_weights(msssim_scales)
         self.lambda_ffl, self.ffl_alpha = float(lambda_ffl), float(ffl_alpha)
-        # optional texture term lambda_style * sum_taps gram_loss(phi(fake_b), phi(real_b)) on a second
-        # frozen VGG19 without tap fusion (models.vgg.StyleLoss: one more VGG forward + backward);
-        # 0 = not built
         self.lambda_style = float(lambda_style)
         self.criterionStyle = StyleLoss(self.criterionVGG) if self.lambda_style > 0 else None
+        self.image_terms = ImageTerms(self.lambda_ssim, ssim_window, self.lambda_msssim, self.msssim_weights,
+                                      self.lambda_ffl, self.ffl_alpha, self.lambda_style, self.criterionStyle)
         self.feat_weights = 4.0 / (n_layers_d + 1)
         self.d_weights = 1.0 / num_d
         self.opt_g = make_adam(net_g.parameters(), lr=lr, betas=(beta1, 0.999))
@@ -179,10 +177,7 @@ class CompressGANStep:
 
     def step(self, real_a, real_b):
         G, D, C = self.net_g, self.net_d, self.net_c
-        if self.lambda_msssim > 0:    # the size rule, before any work of the step
-            ops.ms_ssim_check(real_b.shape, self.ssim_window, len(self.msssim_weights), "lambda_msssim")
-        if self.lambda_ffl > 0:
-            ops.ffl_check(real_b.shape, "lambda_ffl")
+        self.image_terms.check(real_b.shape)   # the size rules, before any work of the step
         if real_a.is_cuda and _native.get_backend() == "native":
             from ..ops import hip
             hip.begin_step()
@@ -204,12 +199,9 @@ class CompressGANStep:
             loss_d = (loss_d_fake + loss_d_real) * 0.5
         # ---- G losses: D frozen (its G-loss gradients are discarded by the reference)
         set_requires_grad(self._d_trainable, False)
-        # fake_b feeds D, VGG and TV: one fan-out node sums their gradients with HIP adds
-        use_ssim = self.lambda_ssim > 0
-        use_msssim = self.lambda_msssim > 0
-        use_ffl = self.lambda_ffl > 0
-        use_style = self.lambda_style > 0
-        fake_d, fake_v, fake_t, *fake_s = ops.fan_out(fake_b, 3 + use_ssim + use_msssim + use_ffl + use_style)
+        # fake_b feeds D, VGG, TV and the image terms: one fan-out node sums their gradients with
+        # HIP adds
+        fake_d, fake_v, fake_t, *fake_s = ops.fan_out(fake_b, 3 + len(self.image_terms))
         pred_fake_g = D(self._d_in(real_a, fake_d))
         # back on before any backward: autograd's AccumulateGrad skips a leaf that no longer
         # requires grad, which would silently drop the D-loss gradients
@@ -237,36 +229,19 @@ class CompressGANStep:
                    and os.environ.get("P2P_VGG_REUSE", "1") != "0" else None)
         vgg_g = self._vgg(fake_v, real_b, fy_real)
         tv = calc_tv_Loss(fake_t)
-        style = self.criterionStyle(fake_s.pop(), real_b) if use_style else None
-        ssim = ops.ssim_loss(fake_s[0], real_b, self.ssim_window) if use_ssim else None
-        ffl = ops.ffl_loss(fake_s.pop(), real_b, self.ffl_alpha) if use_ffl else None
-        msssim = (ops.ms_ssim_loss(fake_s[-1], real_b, self.ssim_window, weights=self.msssim_weights)
-                  if use_msssim else None)
+        extra = self.image_terms.evaluate(fake_s, real_b)
         if native:
-            terms = [loss_g_gan] + ([loss_feat] if feat else []) + [vgg_g, tv]
-            weights = [1.0] + ([1.0] if feat else []) + [self.lambda_vgg, self.lambda_tv]
-            if use_ssim:
-                terms, weights = terms + [ssim], weights + [self.lambda_ssim]
-            if use_msssim:
-                terms, weights = terms + [msssim], weights + [self.lambda_msssim]
-            if use_ffl:
-                terms, weights = terms + [ffl], weights + [self.lambda_ffl]
-            if use_style:
-                terms, weights = terms + [style], weights + [self.lambda_style]
+            terms = [loss_g_gan] + ([loss_feat] if feat else []) + [vgg_g, tv] + [t for _, t, _ in extra]
+            weights = ([1.0] + ([1.0] if feat else []) + [self.lambda_vgg, self.lambda_tv]
+                       + [w for _, _, w in extra])
             loss_g = ops.lincomb_n(terms, weights)
             with torch.no_grad():
                 content = ops.lincomb_n([vgg_g.detach()], [self.lambda_vgg])
         else:
             content = vgg_g * self.lambda_vgg
             loss_g = loss_g_gan + loss_feat + content + tv * self.lambda_tv
-            if use_ssim:
-                loss_g = loss_g + ssim * self.lambda_ssim
-            if use_msssim:
-                loss_g = loss_g + msssim * self.lambda_msssim
-            if use_ffl:
-                loss_g = loss_g + ffl * self.lambda_ffl
-            if use_style:
-                loss_g = loss_g + style * self.lambda_style
+            for _, term, weight in extra:
+                loss_g = loss_g + term * weight
         # ---- updates: G first (its backward also reaches D; those grads are dropped)
         with self._phase("G_bwd_opt"):
             self._zero(self.opt_g, self.reducer_g)
@@ -311,12 +286,5 @@ class CompressGANStep:
         out = {"D": loss_d.detach(), "G_GAN": loss_g_gan.detach(),
                "C": loss_c.detach(), "G_GAN_Feat": torch.as_tensor(loss_feat).detach(),
                "VGG": content.detach(), "TV": tv.detach(), "G": loss_g.detach()}
-        if use_ssim:
-            out["SSIM"] = ssim.detach()
-        if use_msssim:
-            out["MSSSIM"] = msssim.detach()
-        if use_ffl:
-            out["FFL"] = ffl.detach()
-        if use_style:
-            out["Style"] = style.detach()
+        out.update((key, term.detach()) for key, term, _ in extra)
         return out

@@ -24,8 +24,8 @@ import torch
 from .. import _native
 from ..models.compress_gan import MultiscaleDiscriminator
 from ..models.layers import BatchNorm2d
-from ..models.losses import GANLoss
-from ..ops import ffl_check, ffl_loss, l1, ms_ssim_check, ms_ssim_loss, ms_ssim_weights, ssim_loss
+from ..models.losses import GANLoss, ImageTerms
+from ..ops import l1, ms_ssim_weights
 from ..utils.tracing import trace_range
 from .optim import guarded_step, make_adam
 
@@ -44,13 +44,13 @@ class Pix2PixStep:
         self.netG, self.netD = netG, netD
         self.criterionGAN = GANLoss(gan_mode=gan_mode)
         self.lambda_L1 = float(lambda_L1)
-        # optional structural term lambda_ssim * (1 - SSIM(fake_B, real_B)); 0 = not built
+        # optional terms lambda * term(fake_B, real_B), 0 = not built: 1 - SSIM, 1 - MS-SSIM over the
+        # first msssim_scales of the five weights (renormalised, same window), focal frequency loss
         self.lambda_ssim, self.ssim_window = float(lambda_ssim), ssim_window
-        # optional multi-scale term lambda_msssim * (1 - MS-SSIM(fake_B, real_B)) over the first
-        # msssim_scales of the five weights (renormalised), same window; 0 = not built
         self.lambda_msssim, self.msssim_weights = float(lambda_msssim), ms_ssim_weights(msssim_scales)
-        # optional frequency term lambda_ffl * FFL(fake_B, real_B) (focal frequency loss); 0 = not built
         self.lambda_ffl, self.ffl_alpha = float(lambda_ffl), float(ffl_alpha)
+        self.image_terms = ImageTerms(self.lambda_ssim, ssim_window, self.lambda_msssim, self.msssim_weights,
+                                      self.lambda_ffl, self.ffl_alpha)
         self.opt_G = make_adam(netG.parameters(), lr=lr, betas=(beta1, 0.999))
         self.opt_D = make_adam(netD.parameters(), lr=lr, betas=(beta1, 0.999))
         self.reducer_g, self.reducer_d = reducer_g, reducer_d
@@ -126,7 +126,7 @@ class Pix2PixStep:
         from ..models.pix2pix import NLayerDiscriminator, PixelDiscriminator, UnetGenerator
         if self.packed is False or self.fuse_d_batch is False or not self.d_per_sample:
             return False
-        if self.lambda_ssim > 0 or self.lambda_msssim > 0 or self.lambda_ffl > 0:
+        if self.image_terms:
             # the packed step keeps fake_B only inside the pair tensor, whose gradient is
             # produced by D's first-conv dgrad: no tensor for a second image loss to read
             return False
@@ -141,10 +141,7 @@ class Pix2PixStep:
 
     def step(self, real_A, real_B):
         netG, netD = self.netG, self.netD
-        if self.lambda_msssim > 0:    # the size rule, before any work of the step
-            ms_ssim_check(real_B.shape, self.ssim_window, len(self.msssim_weights), "lambda_msssim")
-        if self.lambda_ffl > 0:
-            ffl_check(real_B.shape, "lambda_ffl")
+        self.image_terms.check(real_B.shape)   # the size rules, before any work of the step
         native = real_A.is_cuda and _native.get_backend() == "native"
         if native:
             from ..ops import hip
@@ -251,15 +248,9 @@ class Pix2PixStep:
             loss_G_GAN = self.criterionGAN(pred_fake, True)
             loss_G_L1 = l1(fake_B, real_B) * self.lambda_L1
             loss_G = loss_G_GAN + loss_G_L1
-            if self.lambda_ssim > 0:
-                loss_G_SSIM = ssim_loss(fake_B, real_B, self.ssim_window)
-                loss_G = loss_G + loss_G_SSIM * self.lambda_ssim
-            if self.lambda_msssim > 0:
-                loss_G_MSSSIM = ms_ssim_loss(fake_B, real_B, self.ssim_window, weights=self.msssim_weights)
-                loss_G = loss_G + loss_G_MSSSIM * self.lambda_msssim
-            if self.lambda_ffl > 0:
-                loss_G_FFL = ffl_loss(fake_B, real_B, self.ffl_alpha)
-                loss_G = loss_G + loss_G_FFL * self.lambda_ffl
+            extra = self.image_terms.evaluate([fake_B] * len(self.image_terms), real_B)
+            for _, term, weight in extra:
+                loss_G = loss_G + term * weight
         with self._phase("G_bwd_opt"):
             self._zero(self.opt_G, self.reducer_g)
             loss_G.backward()
@@ -271,10 +262,5 @@ class Pix2PixStep:
             self._guarded_step(self.opt_G, self.reducer_g, loss_G)
         out = {"D": loss_D.detach(), "G_GAN": loss_G_GAN.detach(), "G_L1": loss_G_L1.detach(),
                "G": loss_G.detach()}
-        if self.lambda_ssim > 0:
-            out["G_SSIM"] = loss_G_SSIM.detach()
-        if self.lambda_msssim > 0:
-            out["G_MSSSIM"] = loss_G_MSSSIM.detach()
-        if self.lambda_ffl > 0:
-            out["G_FFL"] = loss_G_FFL.detach()
+        out.update(("G_" + key, term.detach()) for key, term, _ in extra)
         return out

@@ -94,6 +94,38 @@ class FocalFrequencyLoss(nn.Module):
         return ops.ffl_loss(pred, target, self.alpha)
 
 
+class ImageTerms:
+    """The optional image terms of a generator loss, ``weight * term(fake, real)``, in the fixed
+    order ssim, msssim, ffl, style.  Only terms with a weight > 0 are in the table: with every
+    weight 0 it is empty and a step builds and launches nothing for it.  The order is the
+    contract: term i reads the i-th extra ``fan_out`` view (whose backward sums the views'
+    bf16 gradients in view order) and is the i-th appended to the loss composition."""
+
+    def __init__(self, lambda_ssim, ssim_window, lambda_msssim, msssim_weights, lambda_ffl, ffl_alpha,
+                 lambda_style=0.0, style=None):
+        table = (   # (log key, weight, (fake, real) -> scalar, size rule or None)
+            ("SSIM", lambda_ssim, lambda f, r: ops.ssim_loss(f, r, ssim_window), None),
+            ("MSSSIM", lambda_msssim, lambda f, r: ops.ms_ssim_loss(f, r, ssim_window, weights=msssim_weights),
+             lambda shape: ops.ms_ssim_check(shape, ssim_window, len(msssim_weights), "lambda_msssim")),
+            ("FFL", lambda_ffl, lambda f, r: ops.ffl_loss(f, r, ffl_alpha),
+             lambda shape: ops.ffl_check(shape, "lambda_ffl")),
+            ("Style", lambda_style, style, None))
+        self.terms = [t for t in table if t[1] > 0]
+
+    def __len__(self):
+        return len(self.terms)
+
+    def check(self, shape):
+        """The size rules of the active terms: raise before any work of the step."""
+        for *_, rule in self.terms:
+            if rule is not None:
+                rule(shape)
+
+    def evaluate(self, views, real):
+        """[(log key, value, weight)] in table order; term i reads ``views[i]``."""
+        return [(key, fn(v, real), w) for (key, w, fn, _), v in zip(self.terms, views)]
+
+
 class angular_loss(nn.Module):
     """mean(acos(clamp(cos_sim_c(a, b)))) in degrees (networks.py:870-894)."""
 
