@@ -102,6 +102,13 @@ long p2p_gram_ws(int B, int C, int N);
 int p2p_gram_fwd(const void* fx, const void* fy, int B, int C, int N, float* ws, float* d, void* dh, float* loss,
                  hipStream_t st);
 int p2p_gram_bwd(const void* fx, const void* dh, const float* gout, int B, int C, int N, void* dx, hipStream_t st);
+long p2p_lap_signs(int N, int C, int H, int W, int M);
+long p2p_lap_pyr(int N, int C, int H, int W, int M);
+long p2p_lap_ws(int N, int C, int H, int W, int M);
+int p2p_lap_fwd(const void* x, const void* y, int dtype, const long* strides, int N, int C, int H, int W, int M,
+                float* pyr, signed char* signs, float* ws, float* loss, hipStream_t st);
+int p2p_lap_bwd(const signed char* signs, const float* gout, int dtype, const long* strides, int N, int C, int H,
+                int W, int M, float* tmp, void* dx, void* dy, hipStream_t st);
 int p2p_augment_pairs(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
                       int CH, int CW, int dtype, void* out_a, void* out_b, hipStream_t st);
 int p2p_augment_pairs_aa(const void* a, const void* b, const int* params, int N, int H, int W, int B, int LH, int LW,
@@ -1705,6 +1712,60 @@ Tensor gram_loss_bwd(const Tensor& fx, const Tensor& dh, const Tensor& gout) {
   return dx;
 }
 
+// Laplacian-pyramid L1 loss (csrc/lap_loss.hip).  Size rule: 1 to 6 levels, H and W each a
+// multiple of 2^(levels - 1).
+static void check_lap_size(int64_t N, int64_t C, int64_t H, int64_t W, int64_t M, const char* what) {
+  TORCH_CHECK_VALUE(M >= 1 && M <= 6, what, ": 1 to 6 levels, got ", M);
+  const int64_t mult = int64_t(1) << (M - 1);
+  TORCH_CHECK_VALUE(H >= mult && W >= mult && H % mult == 0 && W % mult == 0, what, ": ", M,
+                    " levels need H and W to be multiples of ", mult, ", got ", H, "x", W);
+  TORCH_CHECK(N >= 1 && C >= 1 && N <= 65535 && C * ((H + 31) / 32) <= 65535 && H < (1 << 20) && W < (1 << 20),
+              what, ": N, C * H / 32 <= 65535");
+}
+
+// {loss, the int8 sign pyramid (flat: levels 0 .. M - 1, [N, C, H_j, W_j] each)}: all the
+// backward needs
+std::vector<Tensor> lap_loss_fwd(const Tensor& x, const Tensor& y, int64_t levels) {
+  check_image_pair(x, y, "lap_loss_fwd");
+  check_lap_size(x.size(0), x.size(1), x.size(2), x.size(3), levels, "lap_loss_fwd");
+  const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3), M = (int)levels;
+  auto f32 = x.options().dtype(at::kFloat);
+  Tensor pyr = at::empty({p2p_lap_pyr(N, C, H, W, M)}, f32);   // scratch: dead on return
+  Tensor ws = at::empty({p2p_lap_ws(N, C, H, W, M)}, f32);
+  Tensor signs = at::empty({p2p_lap_signs(N, C, H, W, M)}, f32.dtype(at::kChar));
+  Tensor loss = at::empty({}, f32);
+  check_rc(p2p_lap_fwd(x.data_ptr(), y.data_ptr(), dtype_code(x), image_strides({&x, &y}).data(), N, C, H, W, M,
+                       pyr.data_ptr<float>(), signs.data_ptr<int8_t>(), ws.data_ptr<float>(), loss.data_ptr<float>(),
+                       cur_stream(x)),
+           "lap_loss_fwd");
+  return {loss, signs};
+}
+
+// {dL/dx, dL/dy = -dL/dx} (dy undefined unless need_y) of the [N, C, H, W] = sizes images,
+// allocated with the given strides and dtype (0 = fp32, 1 = bf16): neither image is kept
+std::vector<Tensor> lap_loss_bwd(const Tensor& signs, const Tensor& gout, at::IntArrayRef sizes,
+                                 at::IntArrayRef strides, int64_t dtype, int64_t levels, bool need_y) {
+  TORCH_CHECK(sizes.size() == 4 && strides.size() == 4 && (dtype == 0 || dtype == 1),
+              "lap_loss_bwd: 4 sizes, 4 strides, dtype 0 | 1");
+  check_lap_size(sizes[0], sizes[1], sizes[2], sizes[3], levels, "lap_loss_bwd");
+  const int N = (int)sizes[0], C = (int)sizes[1], H = (int)sizes[2], W = (int)sizes[3], M = (int)levels;
+  TORCH_CHECK(signs.is_cuda() && signs.scalar_type() == at::kChar && signs.is_contiguous() &&
+                  signs.numel() == p2p_lap_signs(N, C, H, W, M),
+              "lap_loss_bwd: the sign pyramid of this forward");
+  Tensor g = loss_gout(gout, "lap_loss_bwd");
+  auto opt = signs.options().dtype(dtype == 1 ? at::kBFloat16 : at::kFloat);
+  Tensor dx = at::empty_strided(sizes, strides, opt);
+  TORCH_CHECK(dx.is_non_overlapping_and_dense(), "lap_loss_bwd: dense gradient strides");
+  Tensor dy;
+  if (need_y) dy = at::empty_strided(sizes, strides, opt);
+  const long st[4] = {(long)strides[0], (long)strides[1], (long)strides[2], (long)strides[3]};
+  Tensor tmp = at::empty({p2p_lap_pyr(N, C, H, W, M)}, signs.options().dtype(at::kFloat));   // T_j, j >= 1
+  check_rc(p2p_lap_bwd(signs.data_ptr<int8_t>(), g.data_ptr<float>(), (int)dtype, st, N, C, H, W, M,
+                       tmp.data_ptr<float>(), dx.data_ptr(), need_y ? dy.data_ptr() : nullptr, cur_stream(signs)),
+           "lap_loss_bwd");
+  return {dx, dy};
+}
+
 // Random resize / crop / flip of cached pairs (csrc/augment.hip).  a, b: the uint8 [N, H, W, 3]
 // cache; params: int32 [B, 4] rows (index, y0, x0, flip).  A CPU table is range-checked here
 // and copied up; a device table is trusted (the kernel clamps each row into range, so a bad
@@ -2335,6 +2396,8 @@ TORCH_LIBRARY(p2p, m) {
   m.def("ffl_loss_bwd(Tensor f, Tensor inv, Tensor gout, int[] strides, int dtype, float alpha, bool need_y) -> Tensor[]");
   m.def("gram_loss_fwd(Tensor fx, Tensor fy) -> Tensor[]");
   m.def("gram_loss_bwd(Tensor fx, Tensor dh, Tensor gout) -> Tensor");
+  m.def("lap_loss_fwd(Tensor x, Tensor y, int levels) -> Tensor[]");
+  m.def("lap_loss_bwd(Tensor signs, Tensor gout, int[] sizes, int[] strides, int dtype, int levels, bool need_y) -> Tensor[]");
   m.def("augment_pairs(Tensor a, Tensor b, Tensor params, int LH, int LW, int CH, int CW, int dtype, bool antialias=False) -> Tensor[]");
   m.def("quantize(Tensor x, int bits) -> Tensor");
   m.def("quantize_unshuffle(Tensor x, int bits, int r, int cp) -> Tensor[]");
@@ -2419,6 +2482,8 @@ TORCH_LIBRARY_IMPL(p2p, CUDA, m) {
   m.impl("ffl_loss_bwd", ffl_loss_bwd);
   m.impl("gram_loss_fwd", gram_loss_fwd);
   m.impl("gram_loss_bwd", gram_loss_bwd);
+  m.impl("lap_loss_fwd", lap_loss_fwd);
+  m.impl("lap_loss_bwd", lap_loss_bwd);
   m.impl("augment_pairs", augment_pairs);
   m.impl("quantize", quantize);
   m.impl("quantize_unshuffle", quantize_unshuffle);

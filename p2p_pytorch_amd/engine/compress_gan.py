@@ -66,7 +66,7 @@ class CompressGANStep:
                  train_c=False, c_phase_backward=False, vgg=None, reducer_g=None,
                  reducer_d=None, reducer_c=None, nan_guard=True, lambda_ssim=0.0,
                  ssim_window="uniform7", lambda_msssim=0.0, msssim_scales=5, lambda_ffl=0.0,
-                 ffl_alpha=1.0, lambda_style=0.0):
+                 ffl_alpha=1.0, lambda_style=0.0, lambda_lap=0.0, lap_levels=5):
         self.net_g, self.net_d, self.net_c = net_g, net_d, net_c
         self.criterionGAN = GANLoss()                      # LSGAN, reference default
         self.criterionVGG = vgg if vgg is not None else VGGLoss()
@@ -82,9 +82,11 @@ class CompressGANStep:
         self.lambda_msssim, self.msssim_weights = float(lambda_msssim), ops.ms_ssim_weights(msssim_scales)
         self.lambda_ffl, self.ffl_alpha = float(lambda_ffl), float(ffl_alpha)
         self.lambda_style = float(lambda_style)
+        self.lambda_lap, self.lap_levels = float(lambda_lap), int(lap_levels)   # Laplacian-pyramid L1
         self.criterionStyle = StyleLoss(self.criterionVGG) if self.lambda_style > 0 else None
         self.image_terms = ImageTerms(self.lambda_ssim, ssim_window, self.lambda_msssim, self.msssim_weights,
-                                      self.lambda_ffl, self.ffl_alpha, self.lambda_style, self.criterionStyle)
+                                      self.lambda_ffl, self.ffl_alpha, self.lambda_style, self.criterionStyle,
+                                      self.lambda_lap, self.lap_levels)
         self.feat_weights = 4.0 / (n_layers_d + 1)
         self.d_weights = 1.0 / num_d
         self.opt_g = make_adam(net_g.parameters(), lr=lr, betas=(beta1, 0.999))

@@ -9,7 +9,7 @@ backward -- SURVEY.md section 5.8):
   3. G phase (D params frozen, so D only back-propagates to its input):
      ``D(cat(A, fake_B))`` vs real label + ``lambda_L1 * |fake_B - B|`` (+ ``lambda_ssim *
      (1 - SSIM(fake_B, B))`` and ``lambda_msssim * (1 - MS-SSIM(fake_B, B))`` when those
-     weights are set, ``lambda_ffl * FFL(fake_B, B)`` likewise) -> backward -> all-reduce G grads -> Adam(G)
+     weights are set, ``lambda_ffl * FFL(fake_B, B)`` and ``lambda_lap * Lap1(fake_B, B)`` likewise) -> backward -> all-reduce G grads -> Adam(G)
 
 The concat of (A, fake_B) is a *virtual* concat on the native path: D's first conv reads
 the two images through two base pointers (``ops.conv2d`` accepts a tuple input).
@@ -40,17 +40,21 @@ class Pix2PixStep:
     def __init__(self, netG, netD, lr=2e-4, beta1=0.5, gan_mode="vanilla", lambda_L1=100.0,
                  reducer_g=None, reducer_d=None, autocast_dtype=None, fuse_d_batch=None,
                  nan_guard=True, packed=None, lambda_ssim=0.0, ssim_window="uniform7",
-                 lambda_msssim=0.0, msssim_scales=5, lambda_ffl=0.0, ffl_alpha=1.0):
+                 lambda_msssim=0.0, msssim_scales=5, lambda_ffl=0.0, ffl_alpha=1.0, lambda_lap=0.0,
+                 lap_levels=5):
         self.netG, self.netD = netG, netD
         self.criterionGAN = GANLoss(gan_mode=gan_mode)
         self.lambda_L1 = float(lambda_L1)
         # optional terms lambda * term(fake_B, real_B), 0 = not built: 1 - SSIM, 1 - MS-SSIM over the
-        # first msssim_scales of the five weights (renormalised, same window), focal frequency loss
+        # first msssim_scales of the five weights (renormalised, same window), focal frequency loss,
+        # Laplacian-pyramid L1 over lap_levels bands
         self.lambda_ssim, self.ssim_window = float(lambda_ssim), ssim_window
         self.lambda_msssim, self.msssim_weights = float(lambda_msssim), ms_ssim_weights(msssim_scales)
         self.lambda_ffl, self.ffl_alpha = float(lambda_ffl), float(ffl_alpha)
+        self.lambda_lap, self.lap_levels = float(lambda_lap), int(lap_levels)
         self.image_terms = ImageTerms(self.lambda_ssim, ssim_window, self.lambda_msssim, self.msssim_weights,
-                                      self.lambda_ffl, self.ffl_alpha)
+                                      self.lambda_ffl, self.ffl_alpha, lambda_lap=self.lambda_lap,
+                                      lap_levels=self.lap_levels)
         self.opt_G = make_adam(netG.parameters(), lr=lr, betas=(beta1, 0.999))
         self.opt_D = make_adam(netD.parameters(), lr=lr, betas=(beta1, 0.999))
         self.reducer_g, self.reducer_d = reducer_g, reducer_d

@@ -94,22 +94,37 @@ class FocalFrequencyLoss(nn.Module):
         return ops.ffl_loss(pred, target, self.alpha)
 
 
+class LaplacianPyramidLoss(nn.Module):
+    """Laplacian-pyramid L1 ("Lap1") loss of (pred, target) (``ops.lap_loss``): the sum over
+    ``levels`` octave bands of their difference of the band's mean absolute value.  H and W:
+    multiples of ``2 ** (levels - 1)``."""
+
+    def __init__(self, levels=5):
+        super().__init__()
+        self.levels = int(levels)
+
+    def forward(self, pred, target):
+        return ops.lap_loss(pred, target, self.levels)
+
+
 class ImageTerms:
     """The optional image terms of a generator loss, ``weight * term(fake, real)``, in the fixed
-    order ssim, msssim, ffl, style.  Only terms with a weight > 0 are in the table: with every
+    order ssim, msssim, ffl, style, lap.  Only terms with a weight > 0 are in the table: with every
     weight 0 it is empty and a step builds and launches nothing for it.  The order is the
     contract: term i reads the i-th extra ``fan_out`` view (whose backward sums the views'
     bf16 gradients in view order) and is the i-th appended to the loss composition."""
 
     def __init__(self, lambda_ssim, ssim_window, lambda_msssim, msssim_weights, lambda_ffl, ffl_alpha,
-                 lambda_style=0.0, style=None):
+                 lambda_style=0.0, style=None, lambda_lap=0.0, lap_levels=5):
         table = (   # (log key, weight, (fake, real) -> scalar, size rule or None)
             ("SSIM", lambda_ssim, lambda f, r: ops.ssim_loss(f, r, ssim_window), None),
             ("MSSSIM", lambda_msssim, lambda f, r: ops.ms_ssim_loss(f, r, ssim_window, weights=msssim_weights),
              lambda shape: ops.ms_ssim_check(shape, ssim_window, len(msssim_weights), "lambda_msssim")),
             ("FFL", lambda_ffl, lambda f, r: ops.ffl_loss(f, r, ffl_alpha),
              lambda shape: ops.ffl_check(shape, "lambda_ffl")),
-            ("Style", lambda_style, style, None))
+            ("Style", lambda_style, style, None),
+            ("LAP", lambda_lap, lambda f, r: ops.lap_loss(f, r, lap_levels),
+             lambda shape: ops.lap_check(shape, lap_levels, "lambda_lap")))
         self.terms = [t for t in table if t[1] > 0]
 
     def __len__(self):

@@ -208,6 +208,19 @@ def gram_loss(fx, fy):
     return ref.gram_loss(fx, fy)
 
 
+lap_check = ref.lap_check
+
+
+def lap_loss(x, y, levels=5):
+    """Laplacian-pyramid L1 loss of two [N, C, H, W] images, differentiable in both: the sum
+    over ``levels`` bands of ``x - y`` of the band's mean absolute value (binomial 5-tap
+    pyramid, edge-replicated; see ``reference.lap_loss``).  ``levels``: 1 to 6; H and W:
+    multiples of ``2 ** (levels - 1)``."""
+    if _native.use_native(x):
+        return _hip().lap_loss(x, y, levels)
+    return ref.lap_loss(x, y, levels)
+
+
 def augment_pairs(a_u8, b_u8, params, load, crop, dtype=torch.bfloat16, antialias=False):
     """Random resize / crop / flip of cached uint8 [N, H, W, 3] pairs: per row (index, y0, x0,
     flip) of the int32 table ``params``, image ``index`` resized to ``load`` (bicubic, >= the

@@ -1939,6 +1939,39 @@ def ffl_loss(x, y, alpha=1.0):
     return FFLLossFn.apply(x, y, float(alpha))
 
 
+class LapLossFn(torch.autograd.Function):
+    """Laplacian-pyramid L1 loss (csrc/lap_loss.hip).  Saves only the int8 sign pyramid (4/3
+    byte per pixel): neither image.  The gradients take the layout ``empty_like`` would give
+    each image; y's is the exact negative of x's, written by the same launch."""
+
+    @staticmethod
+    def forward(ctx, x, y, levels):
+        if y.dtype != x.dtype:
+            y = y.to(x.dtype)
+        loss, signs = P().lap_loss_fwd(x, y, levels)
+        like = torch.empty_like(torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device="meta"))
+        ctx.levels, ctx.sizes, ctx.strides = levels, list(x.shape), list(like.stride())
+        ctx.bf16 = x.dtype == torch.bfloat16
+        ctx.save_for_backward(signs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (signs,) = ctx.saved_tensors
+        nx, ny = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx, gy = P().lap_loss_bwd(signs, gout.float().reshape(1), ctx.sizes, ctx.strides, int(ctx.bf16),
+                                  ctx.levels, ny)
+        return (gx if nx else None), (gy if ny else None), None
+
+
+def lap_loss(x, y, levels=5):
+    from . import reference as ref
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"lap_loss: fp32 or bf16 images, got {x.dtype}")   # no silent upcast
+    ref.lap_check(x.shape, int(levels))
+    return LapLossFn.apply(x, y, int(levels))
+
+
 class GramLossFn(torch.autograd.Function):
     """Gram-matrix style loss (csrc/gram_loss.hip).  Saves fx and the bf16 image of
     D = G(fx) - G(fy) ([B, C, C]); the gradient has the dtype and strides of fx."""

@@ -277,6 +277,70 @@ def ffl_loss(x: torch.Tensor, y: torch.Tensor, alpha: float = 1.0, method: str =
     return (w * p).mean()
 
 
+LAP_MAX_LEVELS = 6
+
+
+def lap_check(shape, levels: int, what: str = "lap_loss"):
+    """The size rule of the Laplacian-pyramid loss: 1 to 6 levels, H and W each a multiple of
+    ``2 ** (levels - 1)`` (every level halves exactly)."""
+    if not 1 <= levels <= LAP_MAX_LEVELS:
+        raise ValueError(f"{what}: 1 to {LAP_MAX_LEVELS} levels, got {levels}")
+    m = 1 << (levels - 1)
+    if shape[-2] < m or shape[-1] < m or shape[-2] % m or shape[-1] % m:
+        raise ValueError(f"{what}: {levels} levels need H and W to be multiples of {m}, "
+                         f"got {shape[-2]}x{shape[-1]}")
+
+
+def _lap_down(g):
+    """Binomial [1, 4, 6, 4, 1] / 16 per axis on the edge-replicated image, at even positions."""
+    C = g.shape[1]
+    k = torch.tensor([1.0, 4.0, 6.0, 4.0, 1.0], dtype=g.dtype, device=g.device) / 16.0
+    w = (k[:, None] * k[None, :]).expand(C, 1, 5, 5).contiguous()
+    return F.conv2d(F.pad(g, (2, 2, 2, 2), mode="replicate"), w, stride=2, groups=C)
+
+
+def _lap_up_axis(g, dim):
+    """up[2i] = (g[i-1] + 6 g[i] + g[i+1]) / 8, up[2i+1] = (g[i] + g[i+1]) / 2, indices clamped."""
+    n = g.shape[dim]
+    lo = torch.cat((g.narrow(dim, 0, 1), g.narrow(dim, 0, n - 1)), dim)
+    hi = torch.cat((g.narrow(dim, 1, n - 1), g.narrow(dim, n - 1, 1)), dim)
+    even, odd = (lo + 6.0 * g + hi) / 8.0, (g + hi) / 2.0
+    shape = list(g.shape)
+    shape[dim] = 2 * n
+    return torch.stack((even, odd), dim + 1).reshape(shape)
+
+
+def lap_bands(x: torch.Tensor, y: torch.Tensor, levels: int = 5):
+    """The ``levels`` bands of the Laplacian pyramid of ``x - y`` (see ``lap_loss``)."""
+    if x.dtype in (torch.bfloat16, torch.float16):
+        x = x.float()
+    y = y.to(x.dtype)
+    lap_check(x.shape, levels)
+    g, bands = x - y, []
+    for _ in range(levels - 1):
+        d = _lap_down(g)
+        bands.append(g - _lap_up_axis(_lap_up_axis(d, 2), 3))
+        g = d
+    return bands + [g]
+
+
+def lap_loss(x: torch.Tensor, y: torch.Tensor, levels: int = 5) -> torch.Tensor:
+    """Laplacian-pyramid L1 loss of two [N, C, H, W] images (the oracle of csrc/lap_loss.hip).
+
+    ``g_0 = x - y``; ``g_{j+1} = D g_j`` with D the separable binomial [1, 4, 6, 4, 1] / 16 on the
+    edge-replicated image sampled at even rows and columns; U doubles each axis (``up[2i] =
+    (g[i-1] + 6 g[i] + g[i+1]) / 8``, ``up[2i+1] = (g[i] + g[i+1]) / 2``, indices clamped).  Bands
+    ``b_j = g_j - U g_{j+1}`` and ``b_{M-1} = g_{M-1}``; the loss is ``sum_j mean |b_j|``, so every
+    octave has the same say (``levels = 1``: plain L1).  H and W: multiples of
+    ``2 ** (levels - 1)``.  Keeps the dtype it is given (half types go to fp32).
+    """
+    bands = lap_bands(x, y, levels)
+    loss = bands[0].abs().mean()
+    for b in bands[1:]:
+        loss = loss + b.abs().mean()
+    return loss
+
+
 def gram_check(shape, what: str = "gram_loss"):
     """The size rule of the Gram-matrix style loss: [B, C, H, W] features with C a multiple of
     64 in [64, 512] (every VGG19 tap) and at least one pixel."""

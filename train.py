@@ -82,6 +82,10 @@ def build_parser():
     p.add_argument("--msssim_scales", type=int, default=5, choices=[1, 2, 3, 4, 5],
                    help="MS-SSIM scales: the first M of the five weights, renormalised; the images need "
                         "min(H, W) >> (M - 1) >= the window size")
+    p.add_argument("--lambda_lap", type=float, default=0.0,
+                   help="weight on the Laplacian-pyramid L1 loss Lap1(fake, real) of the G objective (0 = off)")
+    p.add_argument("--lap_levels", type=int, default=5, choices=[1, 2, 3, 4, 5, 6],
+                   help="Laplacian-pyramid levels M; H and W must each be a multiple of 2^(M - 1)")
     # ---- new
     p.add_argument("--netG", default="expand", help="expand | unet_256 | unet_128 | unet_<levels>")
     p.add_argument("--netD", default=None, help="multiscale | basic | n_layers | pixel")
@@ -241,7 +245,8 @@ def main(argv=None):
                               nan_guard=not opt.no_nan_guard,
                               lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window,
                               lambda_msssim=opt.lambda_msssim, msssim_scales=opt.msssim_scales,
-                              lambda_ffl=opt.lambda_ffl, ffl_alpha=opt.ffl_alpha)
+                              lambda_ffl=opt.lambda_ffl, ffl_alpha=opt.ffl_alpha,
+                              lambda_lap=opt.lambda_lap, lap_levels=opt.lap_levels)
         opt_g, opt_d = trainer.opt_G, trainer.opt_D
     else:
         from p2p_pytorch_amd.engine.compress_gan import CompressGANStep
@@ -254,7 +259,8 @@ def main(argv=None):
                                   lambda_ssim=opt.lambda_ssim, ssim_window=opt.ssim_window,
                                   lambda_msssim=opt.lambda_msssim, msssim_scales=opt.msssim_scales,
                                   lambda_ffl=opt.lambda_ffl, ffl_alpha=opt.ffl_alpha,
-                                  lambda_style=opt.lambda_style)
+                                  lambda_style=opt.lambda_style,
+                                  lambda_lap=opt.lambda_lap, lap_levels=opt.lap_levels)
         opt_g, opt_d = trainer.opt_g, trainer.opt_d
     # the reference's third optimizer / scheduler pair (train.py:243-246, :441-443): over C
     # when --train_c fixes quirk A1, and stepped + checkpointed like the other two
